@@ -18,7 +18,9 @@ parameters are resident in HBM before the timed region.  "ray" = one scene trave
 (primary/reflection RK:114 + shadow RK:153); the per-frame count is the kernel's own exact counter
 (tests check it against the oracle).
 
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps once and prints the headline
+(metric, value, unit, ms_per_step ...); everything below other than value / ms_per_step is measured or checked only
+with --full.  --dump-outputs DIR writes the last timed frame and its ray count as DIR/*.npy (see dump_outputs).
   * value / ms_per_step: K frames enqueued back to back (up to four overlap on the device);
     serial_ms_per_step: the same frames one at a time (render + wait, the reference's
     `await onSubmittedWorkDone`, RR:467), timed separately after the main region.
@@ -81,16 +83,21 @@ def parse():
     ap.add_argument("--serial", action="store_true",
                     help="the MAIN timed region runs one frame at a time (render + wait, RR:467); default: frames "
                          "are enqueued back to back and up to four overlap on the device")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: repeated regions, the one-at-a-time / read-back / loop measurements, the frame "
+                         "check against the oracle, the roofline, the CPU baseline, the clocks and the Node host")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed frame (and its ray count) to DIR as float32 / float64 .npy")
     ap.add_argument("--serial-steps", type=int, default=-1,
-                    help="frames of the separate one-at-a-time measurement (default min(steps, 20); 0: skip)")
+                    help="--full: frames of the separate one-at-a-time measurement (default min(steps, 20); 0: skip)")
     ap.add_argument("--gather", default="root", choices=["root", "all"],
                     help="N > 1: tiles go to rank 0 only (grouped ncclSend/ncclRecv) or to every rank (ncclAllGather)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target CPU time of the oracle sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="--full: target CPU time of the oracle sample")
     ap.add_argument("--repeats", type=int, default=5,
-                    help="the timed region of K steps is run this many times in the one invocation: ms_per_step / value are the FIRST "
-                         "region's (the contract's K steps), ms_per_step_median / _min are taken over all of them")
-    ap.add_argument("--no-node", action="store_true", help="skip the measurement through the Node host (node/bench-frames.js)")
+                    help="--full: the timed region of K steps is run this many times in the one invocation: ms_per_step / value are the "
+                         "FIRST region's (the contract's K steps), ms_per_step_median / _min are taken over all of them (a plain run: once)")
+    ap.add_argument("--no-node", action="store_true", help="--full: skip the measurement through the Node host (node/bench-frames.js)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="--gpus N > 1 without a launcher: print the torch.distributed.run command the ranks would be started with, and exit")
     ap.add_argument("--force-dist", action="store_true",
@@ -296,6 +303,26 @@ def golden_frame(name):
         return None
 
 
+DUMP_BYTES = 48 << 20       # --dump-outputs: a frame larger than this as float32 is written as a seeded sample of its pixels
+
+
+def dump_outputs(path, frame, rays):
+    """What a caller of the timed path receives, for comparing two builds output for output: the frame (H, W, 4) -- its uint8
+    levels as float32 -- as frame.npy, or, if that would exceed DUMP_BYTES, the same pixels (n, 4) at a fixed seeded sample of
+    n = DUMP_BYTES / 24 flat pixel indices as frame_sample.npy with the indices (float64) as frame_sample_pixel.npy; and the
+    frame's ray count (the kernel's counter) as rays.npy.  About 48 MB at most, well under 64 MB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    if frame.size * 4 <= DUMP_BYTES:
+        np.save(os.path.join(path, "frame.npy"), frame.astype(np.float32))
+    else:
+        px = frame.reshape(-1, frame.shape[-1])
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], DUMP_BYTES // (4 * px.shape[1] + 8), replace=False))
+        np.save(os.path.join(path, "frame_sample.npy"), px[idx].astype(np.float32))
+        np.save(os.path.join(path, "frame_sample_pixel.npy"), idx.astype(np.float64))
+    np.save(os.path.join(path, "rays.npy"), np.array([rays], dtype=np.float64))
+
+
 def launch_ranks(a):
     """`python bench.py --gpus N` with N > 1 and no launcher around it (no WORLD_SIZE in the environment): the ranks are started
     as a child `python -m torch.distributed.run` of THIS process, which has not imported torch nor made any HIP call and makes
@@ -489,12 +516,16 @@ def main():
     fence()
     for _ in range(a.warmup):
         step(a.serial)
-    regions = [timed(a.steps, a.serial) for _ in range(max(1, a.repeats))]      # every region: exactly K steps between two fences
+    regions = [timed(a.steps, a.serial) for _ in range(max(1, a.repeats if a.full else 1))]   # every region: exactly K steps between two fences
     elapsed, kms, gms, kframes = regions[0]
     region_ms = [e / a.steps * 1e3 for (e, _, _, _) in regions]
     rays_local = r.stats()["rays"]
     kid_main = r.stats()["kernel_id"]                 # the form the timed frames ran as
-    if a.serial:                      # every rt_wait reports its own batch of one: sample the per-frame times afterwards
+    # the last timed frame, as rank 0 receives it (for --dump-outputs and the checks of --full)
+    frame = None
+    if rank == 0 and (a.full or a.dump_outputs):
+        frame = host_frame[0].numpy() if exchange == "host" else (r.read_frame() if multi else r.read_pixels())
+    if a.serial and a.full:           # every rt_wait reports its own batch of one: sample the per-frame times afterwards
         kms = gms = 0.0
         kframes = 0
         for _ in range(min(a.steps, 8)):
@@ -504,15 +535,14 @@ def main():
 
     # the last timed frame, hashed against the oracle's frame of this config
     check = None
-    gold = None if tri else golden_frame(name)
-    tri_frame = r.read_pixels() if tri and not multi and rank == 0 else None
-    if gold is not None and (not multi or rank == 0 or root < 0):
-        frame = host_frame[0].numpy() if exchange == "host" else (r.read_frame() if multi else r.read_pixels())
+    gold = None if tri or not a.full else golden_frame(name)
+    tri_frame = frame if tri and not multi else None
+    if gold is not None and frame is not None:
         check = {"sha256_matches_oracle_frame": hashlib.sha256(frame.tobytes()).hexdigest() == gold["sha256"],
                  "golden": "tests/golden/frames.json[%s]" % ("C3" if name == "C4" else name)}
 
     # one frame at a time, separately timed
-    ssteps = min(a.steps, 20) if a.serial_steps < 0 else a.serial_steps
+    ssteps = 0 if not a.full else min(a.steps, 20) if a.serial_steps < 0 else a.serial_steps
     serial_ms = None
     serial_regions = None
     if a.serial:
@@ -607,142 +637,14 @@ def main():
         ms_per_step = elapsed / a.steps * 1e3
         value = rays_frame * a.steps / elapsed / 1e6
         label, hierarchy, queue_pipeline = kernel_label(kid_main)
-        # launches of consecutive frames overlap on the device (each on a share of the chip): the chip-level
-        # rate is work per launch / frame period; one frame at a time: / the launch duration.  The two-kernel
-        # brute-force pipeline shares a path queue: its frames are serialised by the library.
-        overlapping = not a.serial and not queue_pipeline
-        roof_ms = ms_per_step if overlapping else kernel_ms
-        flops_alg = FLOP_PER_TEST * N * rays_kernel
-        local_rows = tiles.tiles_of_rank(H, 0, world) * 8
-        hbm_bytes = 4 * W * min(local_rows, H) + 32 * N + 96
-        if tri:     # image store + the scene read once: 160-B triangles, 32-B nodes, 80-B instance records, two f32 lookups
-            hbm_bytes = 4 * W * min(local_rows, H) + 164 * scene.triangleCount + 32 * scene.node_buffer_length() + 84 * len(scene.instances) + 96
-        hbm_gbps = hbm_bytes / (roof_ms * 1e-3) / 1e9
-
-        # executed work of the dominant kernel, from the committed PMC summary (tools/pmc_summary.py)
-        prof, prof_key, estimated = None, None, False
-        tp = os.path.join(ROOT, "profiles", "traffic.json")
-        if os.path.exists(tp):
-            try:
-                tj = json.load(open(tp))
-                prof_key = "%s/%s/v%d/n%d" % (name, a.mode, a.variant, world)
-                prof = tj.get(prof_key)
-                if prof is None and world > 1:      # per-rank launches of the row-tiled frame: 1/world of the one-GPU launch
-                    prof_key = "%s/%s/v%d/n1" % ("C3" if name == "C4" else name, a.mode, a.variant)
-                    prof = tj.get(prof_key)
-                    estimated = prof is not None
-            except Exception:
-                prof = None
-        # a profile is evidence for the build it was taken with: another build's instruction counts are not reported
         from compute_raytracer_amd import abi as _abi
         build_id = _abi.load().rt_build_id().decode()
-        stale = prof is not None and prof.get("build_id") != build_id
-        stale_note = None
-        if stale:
-            stale_note = "profiles/traffic.json[%s] was taken with build %s, this library is build %s: re-run tools/collect_profiles.sh" % (
-                prof_key, prof.get("build_id"), build_id)
-            prof = None
-        executed = (prof or {}).get("executed", {})
-        counts = (prof or {}).get("counts")
-        valu_serial = executed.get("valu_wave_insts_per_launch")               # PMC pass of one-frame-at-a-time launches
-        valu = executed.get("valu_wave_insts_per_launch_in_flight", valu_serial) if overlapping else valu_serial
-        if valu is not None and estimated:
-            valu = valu / world
-            valu_serial = valu_serial / world
-        roof = {"bound": "valu-issue (fp32 vector pipe)", "kernel": label, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                "kernel_ms_avg": kernel_ms, "time_ms": roof_ms,
-                "launches_in_flight": FLIGHT if overlapping else 1}
-        if valu is not None:
-            ach = valu * FLOP_SLOTS_PER_VALU / (roof_ms * 1e-3) / 1e12
-            roof.update({
-                "achieved": ach, "frac": ach / PEAK_FP32_TFLOPS,
-                "valu_wave_insts_per_launch": valu,
-                "from_profile": {"key": prof_key, "files": prof.get("source_files"), "kernel": prof.get("kernel"),
-                                 "per_rank_estimate_insts_over_world": estimated},
-                "traffic": None if estimated else prof.get("hbm_bytes_per_launch"),
-                "basis": "achieved = VALU wave-instructions the kernel executes per launch (PMC SQ_INSTS_VALU, from_profile) x 128 "
-                         "fp32 flop slots (2 SIMD-32 cycles x 32 lanes x 2) / time_ms; peak = 1024 SIMDs x 64 flop/clk x 2.4 GHz. "
-                         "time_ms = frame period with launches_in_flight frames overlapping, else the launch duration.",
-            })
-            if serial_ms is not None and not queue_pipeline:
-                s_ach = valu_serial * FLOP_SLOTS_PER_VALU / (serial_ms * 1e-3) / 1e12
-                roof["serial"] = {"time_ms": serial_ms, "achieved": s_ach, "frac": s_ach / PEAK_FP32_TFLOPS}
-            if counts:
-                # what of the issue slots is the algorithm's own arithmetic: the FMAs of the node / leaf tests of the walk
-                # (8 per test) and the flops of the literal evaluations (25 each, HK:308-311), counted by the counting
-                # builds of the same kernel (tools/count_probe.py); lanes_busy = lane-steps with a live ray / all lane-steps
-                useful_flop = FLOP_PER_NODE_TEST * counts["node_and_leaf_tests"] + FLOP_PER_TEST * counts["literal_tests"]
-                if estimated:
-                    useful_flop /= world
-                u = useful_flop / (roof_ms * 1e-3) / 1e12
-                roof["useful"] = {"achieved": u, "frac": u / PEAK_FP32_TFLOPS, "flop_per_launch": useful_flop,
-                                  "node_and_leaf_tests_per_ray": counts["node_and_leaf_tests"] / max(counts["rays"], 1),
-                                  "literal_tests_per_ray": counts["literal_tests"] / max(counts["rays"], 1),
-                                  "lanes_busy": counts.get("lanes_busy")}
-        else:
-            roof.update({"achieved": None, "frac": None, "traffic": None,
-                         "basis": stale_note or "no PMC pass for %s under profiles/: executed-instruction roofline not available" % prof_key})
-        roof["hbm"] = {"achieved": hbm_gbps, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": hbm_gbps / PEAK_HBM_GBPS,
-                       "bytes_per_launch": hbm_bytes}
-        alg_tf = flops_alg / (roof_ms * 1e-3) / 1e12
-        cpu = None
-        if world == 1 and not a.no_cpu_baseline:
-            cpu = cpu_baseline_tri(cfg, scene, mat, sky, a.cpu_seconds, tri_frame) if tri else cpu_baseline(cfg, scene, sky, a.cpu_seconds)
-        if tri:
-            # The triangle kernel is a pointer chase: a node pair per step, ~17 dependent steps per ray.  Its memory side is
-            # MEASURED (TCP / TCC passes of tools/collect_profiles.sh, profiles/traffic.json[...]["cache"]): `achieved` = L1 -> L2
-            # read requests x 64 B per launch / time against the aggregate L2 bandwidth -- a fraction of a per cent: no
-            # bandwidth binds this kernel, the latency of the dependent loads does (`l2.wait_share`: the part of the
-            # wave-cycles spent in s_waitcnt).  What the lanes REQUEST (counted by the oracle on the sampled tiles: 32-B
-            # nodes, 48-B corner triples, 80-B instance records) is kept as `requested`: the L1 absorbs most of it.
-            valu_view = {k: roof.get(k) for k in ("achieved", "frac", "valu_wave_insts_per_launch", "from_profile", "serial") if k in roof}
-            cache = (prof or {}).get("cache") or {}
-            roof = {"bound": "latency of dependent loads (L1 / L2 gathers)", "kernel": label, "peak": PEAK_L2_GBPS, "unit": "GB/s", "kernel_ms_avg": kernel_ms,
-                    "time_ms": roof_ms, "launches_in_flight": FLIGHT if overlapping else 1, "traffic": (prof or {}).get("hbm_bytes_per_launch"),
-                    "valu": valu_view, "hbm": roof["hbm"], "achieved": None, "frac": None}
-            if cache.get("l2_read_bytes_per_launch"):
-                ach = cache["l2_read_bytes_per_launch"] / (roof_ms * 1e-3) / 1e9
-                roof.update({"achieved": ach, "frac": ach / PEAK_L2_GBPS,
-                             "l2": {"read_bytes_per_launch": cache["l2_read_bytes_per_launch"], "hit_rate": cache.get("l2_hit_rate"),
-                                    "mean_read_latency_cycles": cache.get("mean_l2_read_latency_cycles"),
-                                    "wait_share": (cache["wait_any_per_launch"] / executed["wave_cycles_per_launch"])
-                                    if cache.get("wait_any_per_launch") and executed.get("wave_cycles_per_launch") else None},
-                             "basis": "achieved = TCP_TCC_READ_REQ_sum x 64 B per launch (PMC pass of one-frame-at-a-time launches, from_profile) / time_ms; "
-                                      "peak = aggregate L2 bandwidth (34.5 TB/s).  The kernel is latency-bound: see l2.wait_share and `valu`"})
-            else:
-                roof["basis"] = stale_note or "no TCP / TCC pass for %s under profiles/" % prof_key
-            if cpu is not None:
-                gbytes = cpu["gather_bytes_per_ray"] * rays_kernel
-                roof["requested"] = {"achieved": gbytes / (roof_ms * 1e-3) / 1e9, "frac": gbytes / (roof_ms * 1e-3) / 1e9 / PEAK_L2_GBPS,
-                                     "gather_bytes_per_launch": gbytes, "gathers_per_ray": cpu["per_ray"],
-                                     "note": "bytes the lanes ask for, lane by lane (an upper bound of any cache level's traffic)"}
-            check = {"sampled_tiles_match_oracle": cpu["gpu_rows_match"]} if cpu is not None else None
-            if cfg.get("fixture") and tri_frame is not None:
-                pin = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_pin.json")))
-                check = dict(check or {}, sha256_matches_oracle_frame=hashlib.sha256(tri_frame.tobytes()).hexdigest() == pin["oracle_frame_sha256_white_texture"],
-                             golden="tests/golden/ref_pin.json (the oracle's frame of this scene; it agrees with the reference's screenshot within one "
-                                    "level of 255 on %.2f %% of the pixels that do not depend on the missing texture)"
-                                    % (100 * pin["agreement_levels_of_255_max_over_channels"]["texture_free"]["within1"]))
         out = {
             "metric": ("Mrays/s at %dx%d, %d triangles, %d bounces" % (W, H, scene.triangleCount, B)) if tri else
                       ("Mrays/s at %dx%d, %d spheres, %d bounces" % (W, H, N, B)),
             "value": value, "unit": "Mrays/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
             "ms_per_step": ms_per_step, "frames_per_s": 1e3 / ms_per_step,
-            # the same K steps timed `repeats` times in this invocation (the first is ms_per_step): how far one region is from another
-            "repeats": len(region_ms), "ms_per_step_median": sorted(region_ms)[len(region_ms) // 2], "ms_per_step_min": min(region_ms),
-            "ms_per_step_all": region_ms,
-            "serial_ms_per_step_median": sorted(serial_regions)[len(serial_regions) // 2] if serial_regions else None,
-            "serial_ms_per_step_min": min(serial_regions) if serial_regions else None,
-            # what a caller gets, by how it calls: the reference's loop awaits every frame (RR:467) = serial; a host that also
-            # copies every frame out pays the PCIe read-back; `value` / ms_per_step are frames enqueued back to back
-            "serial_ms_per_step": serial_ms,
-            "serial_value": (rays_frame / (serial_ms * 1e-3) / 1e6) if serial_ms else None,
-            "loop_ms_per_step": loop_ms,          # the reference's own loop through this library, one frame at a time (see above)
-            "readback_ms_per_step": readback_ms,
-            "streamed_readback_ms_per_step": streamed_ms,
-            "animated_ms_per_step": animated_ms,
-            "animated_host_scene_update_ms": animated_host_ms if animated_ms is not None else None,
-            "kernel": {"id": int(kid_main), "name": label, "serial_id": int(kid_serial), "build_id": build_id},
+            "kernel": {"id": int(kid_main), "name": label, "build_id": build_id},
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
             "config": {"workload": ("REF: %dx%d, the reference's own scene in the state of its screenshot info/sample_settings.png (cat + mousey + floor: "
@@ -761,34 +663,168 @@ def main():
                                                            if exchange == "host" else
                                                            " + RCCL %s inside librt355 (rt_render_gather)" %
                                                            ("gather to rank 0" if root == 0 else "all-gather"))},
-            "roofline": roof,
-            "algorithmic_speedup_vs_bruteforce": None if tri else {
-                "value": alg_tf / PEAK_FP32_TFLOPS, "algorithmic_tflops": alg_tf, "flop_per_launch": flops_alg,
-                "note": "25 flop x N spheres x rays per launch / time_ms against the fp32 vector peak: how much faster the frame "
-                        "is produced than a kernel that really examined every (ray, sphere) pair could at that peak"},
-            "frame_check": check,
         }
         if multi:
             out["gather_ms_avg"] = gather_ms
             out["exchange"] = exchange
             if exchange_error:
                 out["exchange_error"] = exchange_error
-        out["scaling_note"] = ("ms_per_step / value: frames enqueued back to back (up to %d in flight); serial_ms_per_step / serial_value: every frame "
-                               "awaited, the reference's loop (src/app.ts:124-127).  BASELINE.json's >= 6x at 8 GPUs is claimed for the frames-in-flight "
-                               "figure; DESIGN.md 6 gives the emulated per-rank times for both." % FLIGHT)
-        if cpu is not None:
-            out["cpu_baseline"] = cpu
-        out["clocks"] = gpu_clocks()
-        # the drop-in in the reference's host language, same workload (C3 and the reference's own scene)
-        if not multi and not a.no_node and not a_no_children() and a.mode == "fast" and a.variant == 0 and name in ("C3", "REF"):
-            nb = node_bench(name, scene, mat, sky, cfg, min(a.steps, 100))
-            out["node"] = nb
-            out["node_loop_ms_per_step"] = nb.get("awaitedMsPerFrame")            # `await renderer.render()` per frame (src/app.ts:124-127)
-            out["node_inflight_ms_per_step"] = nb.get("inflightMsPerFrame")       # rt.render back to back, one await per batch
-            out["node_streamed_readback_ms_per_step"] = nb.get("streamedMsPerFrame")
-            if nb.get("sha256") and check and "sha256_matches_oracle_frame" in check:
-                gold_sha = (golden_frame(name) or {}).get("sha256") if not tri else json.load(open(os.path.join(ROOT, "tests", "golden", "ref_pin.json")))["oracle_frame_sha256_white_texture"]
-                out["node"]["frame_matches_oracle"] = nb["sha256"] == gold_sha
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, frame, rays_frame)
+        if a.full:
+            # launches of consecutive frames overlap on the device (each on a share of the chip): the chip-level
+            # rate is work per launch / frame period; one frame at a time: / the launch duration.  The two-kernel
+            # brute-force pipeline shares a path queue: its frames are serialised by the library.
+            overlapping = not a.serial and not queue_pipeline
+            roof_ms = ms_per_step if overlapping else kernel_ms
+            flops_alg = FLOP_PER_TEST * N * rays_kernel
+            local_rows = tiles.tiles_of_rank(H, 0, world) * 8
+            hbm_bytes = 4 * W * min(local_rows, H) + 32 * N + 96
+            if tri:     # image store + the scene read once: 160-B triangles, 32-B nodes, 80-B instance records, two f32 lookups
+                hbm_bytes = 4 * W * min(local_rows, H) + 164 * scene.triangleCount + 32 * scene.node_buffer_length() + 84 * len(scene.instances) + 96
+            hbm_gbps = hbm_bytes / (roof_ms * 1e-3) / 1e9
+
+            # executed work of the dominant kernel, from the committed PMC summary (tools/pmc_summary.py)
+            prof, prof_key, estimated = None, None, False
+            tp = os.path.join(ROOT, "profiles", "traffic.json")
+            if os.path.exists(tp):
+                try:
+                    tj = json.load(open(tp))
+                    prof_key = "%s/%s/v%d/n%d" % (name, a.mode, a.variant, world)
+                    prof = tj.get(prof_key)
+                    if prof is None and world > 1:      # per-rank launches of the row-tiled frame: 1/world of the one-GPU launch
+                        prof_key = "%s/%s/v%d/n1" % ("C3" if name == "C4" else name, a.mode, a.variant)
+                        prof = tj.get(prof_key)
+                        estimated = prof is not None
+                except Exception:
+                    prof = None
+            # a profile is evidence for the build it was taken with: another build's instruction counts are not reported
+            stale = prof is not None and prof.get("build_id") != build_id
+            stale_note = None
+            if stale:
+                stale_note = "profiles/traffic.json[%s] was taken with build %s, this library is build %s: re-run tools/collect_profiles.sh" % (
+                    prof_key, prof.get("build_id"), build_id)
+                prof = None
+            executed = (prof or {}).get("executed", {})
+            counts = (prof or {}).get("counts")
+            valu_serial = executed.get("valu_wave_insts_per_launch")               # PMC pass of one-frame-at-a-time launches
+            valu = executed.get("valu_wave_insts_per_launch_in_flight", valu_serial) if overlapping else valu_serial
+            if valu is not None and estimated:
+                valu = valu / world
+                valu_serial = valu_serial / world
+            roof = {"bound": "valu-issue (fp32 vector pipe)", "kernel": label, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                    "kernel_ms_avg": kernel_ms, "time_ms": roof_ms,
+                    "launches_in_flight": FLIGHT if overlapping else 1}
+            if valu is not None:
+                ach = valu * FLOP_SLOTS_PER_VALU / (roof_ms * 1e-3) / 1e12
+                roof.update({
+                    "achieved": ach, "frac": ach / PEAK_FP32_TFLOPS,
+                    "valu_wave_insts_per_launch": valu,
+                    "from_profile": {"key": prof_key, "files": prof.get("source_files"), "kernel": prof.get("kernel"),
+                                     "per_rank_estimate_insts_over_world": estimated},
+                    "traffic": None if estimated else prof.get("hbm_bytes_per_launch"),
+                    "basis": "achieved = VALU wave-instructions the kernel executes per launch (PMC SQ_INSTS_VALU, from_profile) x 128 "
+                             "fp32 flop slots (2 SIMD-32 cycles x 32 lanes x 2) / time_ms; peak = 1024 SIMDs x 64 flop/clk x 2.4 GHz. "
+                             "time_ms = frame period with launches_in_flight frames overlapping, else the launch duration.",
+                })
+                if serial_ms is not None and not queue_pipeline:
+                    s_ach = valu_serial * FLOP_SLOTS_PER_VALU / (serial_ms * 1e-3) / 1e12
+                    roof["serial"] = {"time_ms": serial_ms, "achieved": s_ach, "frac": s_ach / PEAK_FP32_TFLOPS}
+                if counts:
+                    # what of the issue slots is the algorithm's own arithmetic: the FMAs of the node / leaf tests of the walk
+                    # (8 per test) and the flops of the literal evaluations (25 each, HK:308-311), counted by the counting
+                    # builds of the same kernel (tools/count_probe.py); lanes_busy = lane-steps with a live ray / all lane-steps
+                    useful_flop = FLOP_PER_NODE_TEST * counts["node_and_leaf_tests"] + FLOP_PER_TEST * counts["literal_tests"]
+                    if estimated:
+                        useful_flop /= world
+                    u = useful_flop / (roof_ms * 1e-3) / 1e12
+                    roof["useful"] = {"achieved": u, "frac": u / PEAK_FP32_TFLOPS, "flop_per_launch": useful_flop,
+                                      "node_and_leaf_tests_per_ray": counts["node_and_leaf_tests"] / max(counts["rays"], 1),
+                                      "literal_tests_per_ray": counts["literal_tests"] / max(counts["rays"], 1),
+                                      "lanes_busy": counts.get("lanes_busy")}
+            else:
+                roof.update({"achieved": None, "frac": None, "traffic": None,
+                             "basis": stale_note or "no PMC pass for %s under profiles/: executed-instruction roofline not available" % prof_key})
+            roof["hbm"] = {"achieved": hbm_gbps, "peak": PEAK_HBM_GBPS, "unit": "GB/s", "frac": hbm_gbps / PEAK_HBM_GBPS,
+                           "bytes_per_launch": hbm_bytes}
+            alg_tf = flops_alg / (roof_ms * 1e-3) / 1e12
+            cpu = None
+            if world == 1 and not a.no_cpu_baseline:
+                cpu = cpu_baseline_tri(cfg, scene, mat, sky, a.cpu_seconds, tri_frame) if tri else cpu_baseline(cfg, scene, sky, a.cpu_seconds)
+            if tri:
+                # The triangle kernel is a pointer chase: a node pair per step, ~17 dependent steps per ray.  Its memory side is
+                # MEASURED (TCP / TCC passes of tools/collect_profiles.sh, profiles/traffic.json[...]["cache"]): `achieved` = L1 -> L2
+                # read requests x 64 B per launch / time against the aggregate L2 bandwidth -- a fraction of a per cent: no
+                # bandwidth binds this kernel, the latency of the dependent loads does (`l2.wait_share`: the part of the
+                # wave-cycles spent in s_waitcnt).  What the lanes REQUEST (counted by the oracle on the sampled tiles: 32-B
+                # nodes, 48-B corner triples, 80-B instance records) is kept as `requested`: the L1 absorbs most of it.
+                valu_view = {k: roof.get(k) for k in ("achieved", "frac", "valu_wave_insts_per_launch", "from_profile", "serial") if k in roof}
+                cache = (prof or {}).get("cache") or {}
+                roof = {"bound": "latency of dependent loads (L1 / L2 gathers)", "kernel": label, "peak": PEAK_L2_GBPS, "unit": "GB/s", "kernel_ms_avg": kernel_ms,
+                        "time_ms": roof_ms, "launches_in_flight": FLIGHT if overlapping else 1, "traffic": (prof or {}).get("hbm_bytes_per_launch"),
+                        "valu": valu_view, "hbm": roof["hbm"], "achieved": None, "frac": None}
+                if cache.get("l2_read_bytes_per_launch"):
+                    ach = cache["l2_read_bytes_per_launch"] / (roof_ms * 1e-3) / 1e9
+                    roof.update({"achieved": ach, "frac": ach / PEAK_L2_GBPS,
+                                 "l2": {"read_bytes_per_launch": cache["l2_read_bytes_per_launch"], "hit_rate": cache.get("l2_hit_rate"),
+                                        "mean_read_latency_cycles": cache.get("mean_l2_read_latency_cycles"),
+                                        "wait_share": (cache["wait_any_per_launch"] / executed["wave_cycles_per_launch"])
+                                        if cache.get("wait_any_per_launch") and executed.get("wave_cycles_per_launch") else None},
+                                 "basis": "achieved = TCP_TCC_READ_REQ_sum x 64 B per launch (PMC pass of one-frame-at-a-time launches, from_profile) / time_ms; "
+                                          "peak = aggregate L2 bandwidth (34.5 TB/s).  The kernel is latency-bound: see l2.wait_share and `valu`"})
+                else:
+                    roof["basis"] = stale_note or "no TCP / TCC pass for %s under profiles/" % prof_key
+                if cpu is not None:
+                    gbytes = cpu["gather_bytes_per_ray"] * rays_kernel
+                    roof["requested"] = {"achieved": gbytes / (roof_ms * 1e-3) / 1e9, "frac": gbytes / (roof_ms * 1e-3) / 1e9 / PEAK_L2_GBPS,
+                                         "gather_bytes_per_launch": gbytes, "gathers_per_ray": cpu["per_ray"],
+                                         "note": "bytes the lanes ask for, lane by lane (an upper bound of any cache level's traffic)"}
+                check = {"sampled_tiles_match_oracle": cpu["gpu_rows_match"]} if cpu is not None else None
+                if cfg.get("fixture") and tri_frame is not None:
+                    pin = json.load(open(os.path.join(ROOT, "tests", "golden", "ref_pin.json")))
+                    check = dict(check or {}, sha256_matches_oracle_frame=hashlib.sha256(tri_frame.tobytes()).hexdigest() == pin["oracle_frame_sha256_white_texture"],
+                                 golden="tests/golden/ref_pin.json (the oracle's frame of this scene; it agrees with the reference's screenshot within one "
+                                        "level of 255 on %.2f %% of the pixels that do not depend on the missing texture)"
+                                        % (100 * pin["agreement_levels_of_255_max_over_channels"]["texture_free"]["within1"]))
+            out.update({
+                # the same K steps timed `repeats` times in this invocation (the first is ms_per_step): how far one region is from another
+                "repeats": len(region_ms), "ms_per_step_median": sorted(region_ms)[len(region_ms) // 2], "ms_per_step_min": min(region_ms),
+                "ms_per_step_all": region_ms,
+                "serial_ms_per_step_median": sorted(serial_regions)[len(serial_regions) // 2] if serial_regions else None,
+                "serial_ms_per_step_min": min(serial_regions) if serial_regions else None,
+                # what a caller gets, by how it calls: the reference's loop awaits every frame (RR:467) = serial; a host that also
+                # copies every frame out pays the PCIe read-back; `value` / ms_per_step are frames enqueued back to back
+                "serial_ms_per_step": serial_ms,
+                "serial_value": (rays_frame / (serial_ms * 1e-3) / 1e6) if serial_ms else None,
+                "loop_ms_per_step": loop_ms,          # the reference's own loop through this library, one frame at a time (see above)
+                "readback_ms_per_step": readback_ms,
+                "streamed_readback_ms_per_step": streamed_ms,
+                "animated_ms_per_step": animated_ms,
+                "animated_host_scene_update_ms": animated_host_ms if animated_ms is not None else None,
+                "roofline": roof,
+                "algorithmic_speedup_vs_bruteforce": None if tri else {
+                    "value": alg_tf / PEAK_FP32_TFLOPS, "algorithmic_tflops": alg_tf, "flop_per_launch": flops_alg,
+                    "note": "25 flop x N spheres x rays per launch / time_ms against the fp32 vector peak: how much faster the frame "
+                            "is produced than a kernel that really examined every (ray, sphere) pair could at that peak"},
+                "frame_check": check,
+            })
+            out["kernel"]["serial_id"] = int(kid_serial)
+            out["scaling_note"] = ("ms_per_step / value: frames enqueued back to back (up to %d in flight); serial_ms_per_step / serial_value: every frame "
+                                   "awaited, the reference's loop (src/app.ts:124-127).  BASELINE.json's >= 6x at 8 GPUs is claimed for the frames-in-flight "
+                                   "figure; DESIGN.md 6 gives the emulated per-rank times for both." % FLIGHT)
+            if cpu is not None:
+                out["cpu_baseline"] = cpu
+            out["clocks"] = gpu_clocks()
+            # the drop-in in the reference's host language, same workload (C3 and the reference's own scene)
+            if not multi and not a.no_node and not a_no_children() and a.mode == "fast" and a.variant == 0 and name in ("C3", "REF"):
+                nb = node_bench(name, scene, mat, sky, cfg, min(a.steps, 100))
+                out["node"] = nb
+                out["node_loop_ms_per_step"] = nb.get("awaitedMsPerFrame")            # `await renderer.render()` per frame (src/app.ts:124-127)
+                out["node_inflight_ms_per_step"] = nb.get("inflightMsPerFrame")       # rt.render back to back, one await per batch
+                out["node_streamed_readback_ms_per_step"] = nb.get("streamedMsPerFrame")
+                if nb.get("sha256") and check and "sha256_matches_oracle_frame" in check:
+                    gold_sha = (golden_frame(name) or {}).get("sha256") if not tri else json.load(open(os.path.join(ROOT, "tests", "golden", "ref_pin.json")))["oracle_frame_sha256_white_texture"]
+                    out["node"]["frame_matches_oracle"] = nb["sha256"] == gold_sha
         sys.stdout.flush()
         os.dup2(stdout_fd, 1)
         print(json.dumps(out), flush=True)

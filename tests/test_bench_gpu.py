@@ -1,12 +1,16 @@
 """bench.py and __graft_entry__.smoke() on the GPU box: the JSON contract, and the N>1 code path
 (rt_comm_init + rt_render_gather: render -> RCCL exchange -> de-interleave inside librt355.so)
 taken with a single rank, its assembled frame hashed against the oracle's golden frame."""
+import hashlib
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from helpers import config_inputs, oracle_render
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -25,7 +29,7 @@ def run_bench(*args, env=None):
 
 
 def test_bench_json_contract():
-    d, _ = run_bench("--steps", "3", "--warmup", "1", "--config", "C2", "--cpu-seconds", "2")
+    d, _ = run_bench("--full", "--steps", "3", "--warmup", "1", "--config", "C2", "--cpu-seconds", "2")
     for k in ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline", "serial_ms_per_step", "frame_check"]:
         assert k in d, k
@@ -42,10 +46,51 @@ def test_bench_json_contract():
     assert abs(d["value"] - d["config"]["rays_per_frame"] / d["ms_per_step"] / 1e3) / d["value"] < 0.02
 
 
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_frame(tmp_path, oracle):
+    """Without --full the line is the headline of the K timed steps alone; --dump-outputs writes what the timed path computed
+    in its last step: C2's whole frame (float32) is the oracle's golden frame, through the one-rank and the N > 1 path;
+    C3's frame is written as a fixed seeded sample of its pixels, the same from run to run, within 64 MB, and the sampled
+    pixels of ten 8-row tiles are the oracle's."""
+    golden = json.load(open(os.path.join(ROOT, "tests", "golden", "frames.json")))
+    for extra in ([], ["--force-dist"]):
+        out = tmp_path / ("c2" + "".join(extra))
+        d, _ = run_bench("--steps", "3", "--warmup", "1", "--config", "C2", "--dump-outputs", str(out), *extra,
+                         env={"MASTER_PORT": "29543"})
+        assert d["steps"] == 3 and d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert d["metric"].startswith("Mrays/s at 1920x1080") and d["ms_per_step"] > 0
+        assert abs(d["value"] - d["config"]["rays_per_frame"] / d["ms_per_step"] / 1e3) / d["value"] < 0.02
+        for k in ("repeats", "serial_ms_per_step", "roofline", "cpu_baseline", "frame_check", "clocks", "node"):
+            assert k not in d, k
+        img = np.load(out / "frame.npy")
+        assert img.dtype == np.float32 and img.shape == (1080, 1920, 4)
+        assert hashlib.sha256(img.astype(np.uint8).tobytes()).hexdigest() == golden["C2"]["sha256"]
+        assert np.load(out / "rays.npy").tolist() == [golden["C2"]["rays"]]
+    dumps = []
+    for k in range(2):
+        out = tmp_path / ("c3_%d" % k)
+        run_bench("--steps", "2", "--warmup", "1", "--dump-outputs", str(out))
+        assert sorted(os.listdir(out)) == ["frame_sample.npy", "frame_sample_pixel.npy", "rays.npy"]
+        assert sum(os.path.getsize(out / f) for f in os.listdir(out)) <= 64 << 20
+        dumps.append([np.load(out / f) for f in sorted(os.listdir(out))])
+    sample, pixel, rays = dumps[0]
+    assert sample.dtype == np.float32 and sample.shape[1] == 4 and pixel.dtype == np.float64 and pixel.shape == sample.shape[:1]
+    assert np.all(np.diff(pixel) > 0) and pixel[0] >= 0 and pixel[-1] < 3840 * 2160 and rays.tolist() == [golden["C3"]["rays"]]
+    assert all(np.array_equal(x, y) for x, y in zip(dumps[0], dumps[1]))
+    cfg, scene = config_inputs("C3")
+    W, H, first, step = cfg["width"], cfg["height"], 13, 27                   # tiles 13, 40, ..., 256 of 270
+    ref, _, _ = oracle_render(oracle, scene, W, H, cfg["bounces"], tile_first=first, tile_step=step,
+                              threads=min(16, len(os.sched_getaffinity(0))))
+    p = pixel.astype(np.int64)
+    tile = p // W // 8
+    inside = (tile >= first) & ((tile - first) % step == 0)
+    assert inside.sum() > 10000
+    assert np.array_equal(sample[inside], ref.reshape(-1, 4)[p[inside]].astype(np.float32))
+
+
 def test_bench_headline_roofline_is_an_executed_fraction_below_one():
     """roofline.frac prices what the kernel executes (PMC instruction count from the
     committed profile) and is <= 1; the algorithmic brute-force rate is reported apart."""
-    d, _ = run_bench("--steps", "8", "--warmup", "2", "--no-cpu-baseline")
+    d, _ = run_bench("--full", "--steps", "8", "--warmup", "2", "--no-cpu-baseline")
     fr = json.load(open(os.path.join(ROOT, "tests", "golden", "frames.json")))["C3"]
     assert d["config"]["rays_per_frame"] == fr["rays"] and d["frame_check"]["sha256_matches_oracle_frame"] is True
     r = d["roofline"]
@@ -85,7 +130,7 @@ def test_bench_headline_roofline_is_an_executed_fraction_below_one():
 def test_bench_distributed_path_with_one_rank():
     fr = json.load(open(os.path.join(ROOT, "tests", "golden", "frames.json")))["C2"]
     for gather in ("root", "all"):
-        d, err = run_bench("--steps", "2", "--warmup", "1", "--config", "C2", "--no-cpu-baseline", "--force-dist",
+        d, err = run_bench("--full", "--steps", "2", "--warmup", "1", "--config", "C2", "--no-cpu-baseline", "--force-dist",
                            "--gather", gather, env={"MASTER_PORT": "29541"})
         assert d["frame_check"]["sha256_matches_oracle_frame"] is True, gather
         assert d["config"]["rays_per_frame"] == fr["rays"] and "cpu_baseline" not in d
@@ -97,7 +142,7 @@ def test_bench_two_ranks_rehearsed_on_one_device():
     torch.distributed.run), RT355_BENCH_ONE_DEVICE puts both on device 0.  RCCL refuses two ranks of one device: every rank
     falls back TOGETHER to the labelled host exchange (rows read back, all-gathered over gloo), and the frame the two ranks'
     interleaved tiles make -- 135 tiles: 68 and 67, ragged -- is the oracle's.  (Should RCCL ever accept it: the RCCL path, same frame.)"""
-    d, err = run_bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "C2", "--no-cpu-baseline", "--repeats", "1",
+    d, err = run_bench("--full", "--gpus", "2", "--steps", "2", "--warmup", "1", "--config", "C2", "--no-cpu-baseline", "--repeats", "1",
                        env={"RT355_BENCH_ONE_DEVICE": "1"})
     assert d["n_gpus"] == 2 and d["exchange"] in ("host", "rccl")
     if d["exchange"] == "host":
@@ -118,7 +163,7 @@ def test_bench_distributed_path_pipelines_hierarchy_frames():
     sets (render -> RCCL exchange -> assemble, all inside rt_render_gather), the assembled frame is the
     golden one."""
     fr = json.load(open(os.path.join(ROOT, "tests", "golden", "frames.json")))["C3"]
-    d, err = run_bench("--steps", "6", "--warmup", "1", "--config", "C3", "--no-cpu-baseline", "--force-dist",
+    d, err = run_bench("--full", "--steps", "6", "--warmup", "1", "--config", "C3", "--no-cpu-baseline", "--force-dist",
                        env={"MASTER_PORT": "29542"})
     assert d["frame_check"]["sha256_matches_oracle_frame"] is True
     assert d["config"]["rays_per_frame"] == fr["rays"]
@@ -126,7 +171,7 @@ def test_bench_distributed_path_pipelines_hierarchy_frames():
 
 
 def test_bench_serial_mode_times_single_launches():
-    d, _ = run_bench("--steps", "4", "--warmup", "1", "--config", "C3", "--no-cpu-baseline", "--serial")
+    d, _ = run_bench("--full", "--steps", "4", "--warmup", "1", "--config", "C3", "--no-cpu-baseline", "--serial")
     r = d["roofline"]
     assert r["launches_in_flight"] == 1 and d["config"]["frames_in_flight"] == 1
     assert abs(r["time_ms"] - r["kernel_ms_avg"]) < 1e-9
@@ -138,7 +183,7 @@ def test_bench_reference_scene_config():
     """`--config REF`: the reference's own scene in the state of its screenshot (tests/golden/ref_scene.npz), the window and
     bounce count its overlay reports "6 ms" for; the timed frame is the oracle's frame, which is the screenshot's outside
     the missing texture; an animated frame (instances rewritten every frame, RR:169-192) is reported beside the static one."""
-    d, _ = run_bench("--steps", "12", "--warmup", "2", "--config", "REF", "--cpu-seconds", "3")
+    d, _ = run_bench("--full", "--steps", "12", "--warmup", "2", "--config", "REF", "--cpu-seconds", "3")
     assert "12604 triangles" in d["metric"] and d["config"]["workload"].startswith("REF: 1344x846")
     assert d["frame_check"]["sha256_matches_oracle_frame"] is True and d["frame_check"]["sampled_tiles_match_oracle"] is True
     assert d["kernel"]["name"] == "trace_triangles"
@@ -154,7 +199,7 @@ def test_bench_triangle_config_prices_gathers_against_l2():
     `--config TRI` (12.8 k procedural triangles, the reference screenshot's window, 4 bounces) with a
     bytes-based roofline (32-B node + 160-B triangle + 80-B instance gathers per ray, counted by the
     oracle on the sampled tiles, against the L2 roof) and the GPU's sampled rows checked against the oracle."""
-    d, _ = run_bench("--steps", "6", "--warmup", "2", "--config", "TRI", "--cpu-seconds", "4")
+    d, _ = run_bench("--full", "--steps", "6", "--warmup", "2", "--config", "TRI", "--cpu-seconds", "4")
     assert "triangles" in d["metric"] and d["config"]["rays_per_frame"] > 1344 * 846
     r = d["roofline"]
     assert r["bound"].startswith("latency") and r["unit"] == "GB/s" and r["peak"] == 34500.0

@@ -15,7 +15,10 @@ from compute_raytracer_amd.soup import js_parse_float, parse_obj
 from helpers import obj_floor, obj_uv_sphere, tri_buffers, triangle_scene
 
 F = np.float32
-REF_MODELS = "/root/reference/src/assets/models"
+REF_SCENE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ref_scene.npz")
+# the reference's three meshes (cat, mousey, floor) with the descriptors its scene loads them with, told apart by colour
+REF_MESHES = (([.8, .6, .7, 1], dict(alignBottom=True, scale=0.1)), ([1, 1, 1, .3], dict(alignBottom=True, scale=0.025)),
+              ([1, 1, 1, 1], dict(scale=10)))
 
 
 # ---- gl-matrix restatement (scalar form, kept as the yardstick of the array forms in instances.py) -----------
@@ -115,15 +118,58 @@ def test_soup_loader_quirks():
     assert s.position[0, 0, 0] == -float(F(float(F(0.1)) / 2))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MODELS), reason="reference assets not present")
+def obj_text(records):
+    """OBJ text of packed triangle records (T, 40): one v / vt / vn line per corner, and two records that are the fan
+    (a, b, c), (a, c, d) of one quad written as the face "f a b c d" again.  -> (text, the records in the order the faces
+    yield them, number of quads)."""
+    key = lambda r, c: r[12 * c:12 * c + 10].tobytes()
+    by_first_edge = {}
+    for i, r in enumerate(records):
+        by_first_edge.setdefault((key(r, 0), key(r, 1)), []).append(i)
+    used = np.zeros(len(records), dtype=bool)
+    num = lambda xs: " ".join(repr(float(x)) for x in xs)
+    lines, order, n, quads = ["# rebuilt from tests/golden/ref_scene.npz", "s 1"], [], 0, 0
+    for i, r in enumerate(records):
+        if used[i]:
+            continue
+        used[i] = True
+        order.append(i)
+        corners = [r[0:12], r[12:24], r[24:36]]
+        for j in by_first_edge.get((key(r, 0), key(r, 2)), []):
+            if not used[j]:
+                used[j] = True
+                order.append(j)
+                corners.append(records[j][24:36])
+                quads += 1
+                break
+        for c in corners:
+            lines += ["v " + num(c[0:3]), "vt " + num(c[8:10]), "vn " + num(c[4:7])]
+        lines.append("f " + " ".join("%d/%d/%d" % (k, k, k) for k in range(n + 1, n + 1 + len(corners))))
+        n += len(corners)
+    return "\n".join(lines) + "\n", records[order], quads
+
+
 def test_reference_scene_triangle_count():
     """The reference's own scene: 428 + 12,174 + 2 = 12,604 triangles, the 'Primitive count' of
-    info/sample_settings.png -- the one number of the reference that pins the OBJ loader."""
-    counts = [parse_obj(open(os.path.join(REF_MODELS, f), newline="").read(), d).count for f, d in
-              (("cat.obj", dict(color=[.8, .6, .7, 1], alignBottom=True, scale=0.1)),
-               (os.path.join("mousey", "mousey.obj"), dict(color=[1, 1, 1, .3], alignBottom=True, scale=0.025)),
-               ("flat.obj", dict(color=[1, 1, 1, 1], scale=10)))]
-    assert counts == [428, 12174, 2]
+    info/sample_settings.png.  The committed scene (tests/golden/ref_scene.npz) holds the three meshes as the OBJ loader
+    made them from the reference's files (tests/golden/make_ref_scene.py); each mesh, written back as OBJ text with the
+    fans of its quads rejoined, parses to the same number of triangles and to its own records."""
+    tri = np.load(REF_SCENE)["triangles"]
+    counts, quads = [], []
+    for color, d in REF_MESHES:
+        text, want, q = obj_text(tri[np.all(tri[:, 36:40] == np.float32(color), axis=1)])
+        s = parse_obj(text, dict(d, color=color))
+        counts.append(s.count)
+        quads.append(q)
+        assert s.count == len(want)
+        got = s.pack()
+        for c in range(3):
+            assert np.array_equal(got[:, 12 * c + 4:12 * c + 12], want[:, 12 * c + 4:12 * c + 12])     # normal, uv
+        assert np.array_equal(got[:, 36:40], want[:, 36:40])
+        # positions: the loader's shift and scale of the (already placed) cloud -- the same translation for every corner
+        off = s.position / d["scale"] - want[:, :36].reshape(-1, 3, 12)[:, :, 0:3].astype(np.float64)
+        assert np.ptp(off, axis=(0, 1)).max() < 1e-9
+    assert counts == [428, 12174, 2] and quads[0] > 0 and quads[1] > 0          # the floor's two faces are triangles
 
 
 # ---- bottom-level and top-level trees ------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-timeout -k 10 250 python bench.py --config C3 --steps 100 --warmup 5 > gpurun_out/r04/bench/C3_steps100.json 2> gpurun_out/r04/bench/C3_steps100.err
+OUT=${OUT:-results/r04/bench}; mkdir -p $OUT
+timeout -k 10 250 python bench.py --full --config C3 --steps 100 --warmup 5 > $OUT/C3_steps100.json 2> $OUT/C3_steps100.err || exit 1
 for cfg in C3 C5; do
   export KNOB_CONFIG=$cfg KNOB_BATCH=$([ $cfg = C5 ] && echo 8 || echo 64)
   for w in 1 8; do
