@@ -81,3 +81,245 @@ def ref_fixture():
     canvas = np.array(Image.open(os.path.join(g, "ref_canvas.png")).convert("RGB"), dtype=np.uint8)
     pin = json.load(open(os.path.join(g, "ref_pin.json")))
     return scene, sky, int(d["W"]), int(d["H"]), int(d["maxBounces"]), canvas, pin
+
+
+# ---- triangle scenes made by hand, and the top-level trees and stack forms of the triangle kernel (tests/test_triangles_gpu.py,
+# tests/test_work_list_gpu.py) ----
+def random_sky(seed, w=8, h=8):
+    rng = np.random.default_rng(seed)
+    m = rt.CubemapMaterial()
+    m.faces = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(6)]
+    return m
+
+
+def spine_scene(depth):
+    """A BLAS no builder would make: a spine of `depth` inner nodes, each with a leaf as its FARTHER child, so that the
+    walk pushes one entry per level -- beyond the eight slots the persistent kernel keeps in LDS, and beyond the twenty the
+    reference's stack has at all (RK:71; RK:303-306 pushes without a guard: the index clamps to the last slot, and the pops
+    that follow read that slot again and again).  One triangle per leaf, each covering its own part of the view."""
+    base = 1                                                    # tlasNodesMax of one instance
+    nodes = np.zeros((1 + 2 * depth, 8), np.float32)            # S_0, then the pairs (A_k, S_{k+1}); the last "S" is a leaf
+    tris = np.zeros((depth + 1, 40), np.float32)
+    def box(i, lo, hi, left, count):
+        nodes[i, 0:3] = lo; nodes[i, 3] = left; nodes[i, 4:7] = hi; nodes[i, 7] = count
+    box(0, [-9, -9, -1.0], [9, 9, 5.0], base + 1, 0)
+    for k in range(depth):
+        a, s = 1 + 2 * k, 2 + 2 * k
+        box(a, [-9, -9, -3.0], [9, 9, -2.0], k, 1)                                   # leaf A_k: lookup slot k
+        if k + 1 < depth: box(s, [-9, -9, -1.0], [9, 9, 5.0], base + s + 1, 0)       # S_{k+1}
+        else: box(s, [-9, -9, -1.0], [9, 9, 5.0], depth, 1)                          # the bottom: a leaf inside the near box
+    for k in range(depth + 1):
+        z = -2.05 - 0.9 * k / depth if k < depth else -0.5
+        x0 = -8.0 + 16.0 * ((k * 7) % (depth + 1)) / (depth + 1)
+        w = 3.0 if k < depth else 40.0
+        # front face towards +z (RK:359 culls det < 1e-5)
+        for c, (x, y) in enumerate([(x0, -8.0), (x0 + w, -8.0), (x0 + w / 2, 9.0)]):
+            tris[k, 12 * c:12 * c + 3] = [x, y, z]
+            tris[k, 12 * c + 4:12 * c + 7] = [0, 0, 1]
+            tris[k, 12 * c + 8:12 * c + 10] = [c / 2.0, c % 2]
+        tris[k, 36:40] = [0.2 + 0.8 * ((k * 5) % 7) / 7.0, 0.3 + 0.7 * ((k * 3) % 5) / 5.0, 0.9 - 0.6 * (k % 4) / 4.0, 1.0 if k % 3 else 0.5]
+    d = dict(triangles=tris, blas_nodes=nodes, tri_lookup=np.arange(depth + 1, dtype=np.float32),
+             mesh_root=np.array([base]), mesh_box_lo=np.array([[-9.0, -9.0, -3.0]]), mesh_box_hi=np.array([[9.0, 9.0, 5.0]]),
+             inst_mesh=np.array([0]), inst_position=np.array([[0.0, 0.0, 0.0]]), inst_eulers=np.array([[0.0, 0.0, 0.0]]),
+             inst_speed=np.array([[0.0, 0.0, 0.0]]), camera_position=np.array([0.0593, 2.692, 3.293]),
+             camera_eulers=np.array([0.0, 106.0, 270.0], np.float32), light=np.array([0.0, 5.0, 6.0, 3.0, 0.3]))
+    return rt.SceneRaytracing.from_packed(d)
+
+
+
+def deepen_top_level(scene, levels):
+    """The frame's top-level tree under `levels` extra inner nodes: each new node has the old tree (one level down) as its first
+    child and a leaf far away from everything (instance 0 again: never entered) as its second.  Same picture, a deeper walk."""
+    t = np.asarray(scene.frame["tlas_nodes"], np.float32).reshape(-1, 8)
+    n_old, extra = t.shape[0], 2 * levels
+    assert n_old + extra <= scene.tlasNodesMax
+    out = np.zeros((n_old + extra, 8), np.float32)
+    for k in range(levels):                                  # node 0 and the chain nodes at 1, 3, 5, ...: children at (2k+1, 2k+2)
+        i = 0 if k == 0 else 2 * k - 1
+        out[i] = [-1e4, -1e4, -1e4, 2 * k + 1, 1e4, 1e4, 1e4, 0]
+        out[2 * k + 2] = [9e3, 9e3, 9e3, 0, 9.1e3, 9.1e3, 9.1e3, 1]      # the far leaf
+    base = 2 * levels - 1                                    # where the old root goes; the rest of the old tree behind the chain
+    remap = lambda i: base if i == 0 else extra + i
+    for i in range(n_old):
+        row = t[i].copy()
+        if row[7] == 0:
+            row[3] = remap(int(row[3]))                      # old children sit side by side at left, left + 1 (left >= 1)
+        out[remap(i)] = row
+    scene.frame["tlas_nodes"] = out
+
+
+def expected_form(scene, mat):
+    """rt_tlas_fit.h restated: the stack form the library must pick for the frame's top-level tree (tiny 2, small 1, neither 0)."""
+    nodes = tri_buffers(scene, mat)["nodes"]
+    n = len(nodes)
+    def u32f(f):
+        f = float(f)
+        return 0 if not f > 0.0 else (4294967295 if f >= 4294967040.0 else int(f))
+    def fits(max_depth, max_nodes):
+        todo = [(0, 0)]
+        while todo:
+            i, d = todo.pop()
+            i = min(i, n - 1)
+            if i >= max_nodes: return False
+            if u32f(nodes[i, 7]) != 0: continue
+            if d >= max_depth: return False
+            left = u32f(nodes[i, 3])
+            todo += [(left, d + 1), ((left + 1) & 0xFFFFFFFF, d + 1)]
+        return True
+    if len(scene.instances) > 16: return 0
+    if len(scene.instances) > 12: return 4 if fits(8, 32) else 0       # 13-16 instances: the form that stages sixteen records
+    if len(scene.instances) <= 4 and fits(3, 8): return 2
+    if fits(4, 16): return 1
+    if fits(8, 24): return 3
+    return 4 if fits(8, 32) else 0
+
+
+def leafy_scene(per_leaf, wild=False):
+    """spine_scene's tree of depth 9 with `per_leaf` triangles in every leaf, side by side; wild: one leaf's first slot lies far
+    beyond the lookup table (the oracle clamps it to the last slot; 14 bits would wrap it)."""
+    depth = 9                                                    # spine_scene's tree with `per_leaf` triangles in every leaf, side by side
+    nodes = np.zeros((1 + 2 * depth, 8), np.float32)
+    tris = np.zeros(((depth + 1) * per_leaf, 40), np.float32)
+    def box(i, lo, hi, left, count):
+        nodes[i, 0:3] = lo; nodes[i, 3] = left; nodes[i, 4:7] = hi; nodes[i, 7] = count
+    box(0, [-9, -9, -1.0], [9, 9, 5.0], 2, 0)
+    for k in range(depth):
+        a, sidx = 1 + 2 * k, 2 + 2 * k
+        box(a, [-9, -9, -3.0], [9, 9, -2.0], k * per_leaf, per_leaf)
+        if k + 1 < depth: box(sidx, [-9, -9, -1.0], [9, 9, 5.0], 1 + sidx + 1, 0)
+        else: box(sidx, [-9, -9, -1.0], [9, 9, 5.0], depth * per_leaf, per_leaf)
+    for k in range(depth + 1):
+        for j in range(per_leaf):
+            z = (-2.05 - 0.9 * k / depth if k < depth else -0.5) - 0.01 * j
+            x0 = -8.0 + 16.0 * ((k * 7) % (depth + 1)) / (depth + 1) + 0.7 * j
+            w = 2.0 if k < depth else 30.0
+            t = k * per_leaf + j
+            for c, (x, y) in enumerate([(x0, -8.0), (x0 + w, -8.0), (x0 + w / 2, 9.0)]):
+                tris[t, 12 * c:12 * c + 3] = [x, y, z]
+                tris[t, 12 * c + 4:12 * c + 7] = [0, 0, 1]
+                tris[t, 12 * c + 8:12 * c + 10] = [c / 2.0, c % 2]
+            tris[t, 36:40] = [0.2 + 0.8 * ((t * 5) % 7) / 7.0, 0.3 + 0.7 * ((t * 3) % 5) / 5.0, 0.9 - 0.6 * (t % 4) / 4.0, 1.0 if t % 3 else 0.5]
+    if wild:
+        nodes[5, 3] = 30000.0
+    dd = dict(triangles=tris, blas_nodes=nodes, tri_lookup=np.arange(tris.shape[0], dtype=np.float32),
+              mesh_root=np.array([1]), mesh_box_lo=np.array([[-9.0, -9.0, -3.0]]), mesh_box_hi=np.array([[9.0, 9.0, 5.0]]),
+              inst_mesh=np.array([0]), inst_position=np.array([[0.0, 0.0, 0.0]]), inst_eulers=np.array([[0.0, 0.0, 0.0]]),
+              inst_speed=np.array([[0.0, 0.0, 0.0]]), camera_position=np.array([0.0593, 2.692, 3.293]),
+              camera_eulers=np.array([0.0, 106.0, 270.0], np.float32), light=np.array([0.0, 5.0, 6.0, 3.0, 0.3]))
+    return rt.SceneRaytracing.from_packed(dd)
+
+
+# ---- the work-list rule (rt_triangles.hip: order_hist), restated: quarter-octave classes, half / twice the throughput time, the caps ----
+def cost_class(c):
+    c = int(c)
+    if c < 4:
+        return c
+    e = c.bit_length() - 1
+    return 4 * e + ((c >> (e - 2)) & 3) - 4
+
+
+def model(cost, wave_slots, mult4=1, mult16=4, cap16=64):
+    n = len(cost)
+    cls = np.array([cost_class(c) for c in cost])
+    total = int(np.asarray(cost, np.uint64).sum())
+    thr = total // (2 * max(wave_slots, 1))
+    cls_of = lambda v: cost_class(min(v, 0xFFFFFFFF))
+    above = lambda k: int((cls > k).sum())
+    split, split16 = above(cls_of(mult4 * thr)), above(cls_of(mult16 * thr))
+    if above(cls_of(4 * thr)) == 0:
+        split = split16 = 0
+    most, most16 = min(n // 16, 1024), min(n // 64, cap16)
+    split16 = min(split16, most16)
+    split = max(min(split, most), split16)
+    return split - split16, split16, cls
+
+
+# ---- awaited triangle frames with a work list (tests/test_work_list_gpu.py, tests/test_work_list_scenes_cpu.py) ----
+# From 4,096 tiles on (rt_ctx.h: kOrderMinTiles) an awaited frame renders from the work list the previous frame on its stream left.
+# 517 x 509: 65 x 64 = 4,160 tiles, the last column and the last row ragged.
+WL_W, WL_H = 517, 509
+WL_BOUNCES = 3
+WL_SEED = 21
+
+# Scenes that reach each instantiation of the kernel an awaited frame can take (rt_triangles.hip: rt_launch_triangles):
+# name -> (n_models, extra top-level levels, how the buffers are changed, variant, the small forms are possible).
+#   form1 / form3: trace_roles<SMALL 1 / 3> where the list splits tiles, trace_triangles where it does not;
+#   form4: 13-16 instances;  form0_pairs: a lookup table longer than the instance list keeps the twenty-slot form;
+#   pairs_wide: leaves of four triangles (pair records without 16-bit packing);  packed: more than 16 instances, no pair records;
+#   node_buffer: variant 6, the reference's node buffer;  unpacked: a triangle lookup table over 65,536 entries;
+#   wide_stack: a node buffer of more than 65,536 nodes (the uint32_t stack).
+WORK_LIST_CASES = {
+    "form1": (3, 0, None, 0, True),
+    "form3": (9, 5, None, 0, True),
+    "form4": (14, 0, None, 0, True),
+    "form0_pairs": (3, 0, "double_lookup", 0, True),
+    "pairs_wide": (None, 0, "leafy4", 0, False),
+    "packed": (20, 0, None, 0, True),
+    "node_buffer": (3, 0, None, 6, False),
+    "unpacked": (2, 0, "pad_tri_lookup", 0, False),
+    "wide_stack": (2, 0, "pad_nodes", 0, False),
+}
+ROLES_CASES = ("form1", "form3")
+
+
+class WorkListCase:
+    """A scene of WORK_LIST_CASES and its camera path: advance() turns the models and moves the camera (every frame differs
+    from the one four frames earlier: a tile a list skipped cannot pass on an older frame's pixels), then applies the case's
+    changes to the frame's buffers.  form(): the stack form the library must report for an awaited frame."""
+
+    def __init__(self, name, seed=WL_SEED):
+        n_models, self.deepen, self.change, self.variant, self.small = WORK_LIST_CASES[name]
+        self.name = name
+        if self.change == "leafy4":
+            self.scene = leafy_scene(4)
+            self.mat = rt.Material(np.random.default_rng(4).integers(0, 256, (8, 8, 4), dtype=np.uint8))
+        else:
+            rings, sectors = (7, 9) if self.change in ("pad_tri_lookup", "pad_nodes") else (6, 8)
+            self.scene, self.mat = triangle_scene(seed=seed, n_models=n_models, rings=rings, sectors=sectors)
+        if self.change == "pad_tri_lookup":
+            self.scene.static["tri_lookup"] = np.concatenate([np.asarray(self.scene.static["tri_lookup"], np.float32),
+                                                              np.zeros(70000, np.float32)])
+        if self.change == "pad_nodes":              # unused nodes behind the trees: the buffer, not the walk, is over 65,536 nodes
+            nodes = np.asarray(self.scene.static["blas_nodes"], np.float32)
+            self.scene.static["blas_nodes"] = np.concatenate([nodes, np.zeros((70000, 8), np.float32)])
+            self.scene.blasNodesUsed = self.scene.static["blas_nodes"].shape[0]
+
+    def advance(self, dt=0.15, forwards=0.03, right=0.02):
+        s = self.scene
+        s.update(dt)
+        s.camera.move(forwards, right)
+        levels = min(self.deepen, (s.tlasNodesMax - len(s.frame["tlas_nodes"])) // 2)
+        if levels:
+            deepen_top_level(s, levels)
+        if self.change == "double_lookup":          # every top-level leaf names its instances through a copy of the table
+            look = np.asarray(s.frame["blas_lookup"], np.float32)
+            s.frame["blas_lookup"] = np.concatenate([look, look])
+            t = np.asarray(s.frame["tlas_nodes"], np.float32).copy()
+            t[t[:, 7] > 0, 3] += len(look)
+            s.frame["tlas_nodes"] = t
+
+    def form(self):
+        want = expected_form(self.scene, self.mat) if self.small and self.change != "double_lookup" else 0
+        return 1 if want == 2 else want
+
+
+RAGGED_STEP = (0.1, 0.01, 0.005)                  # advance()'s turn and camera step on the path of ragged_edge_case
+
+
+def ragged_edge_case():
+    """form1's scene with the camera turned left and up: the meshes sit in the ragged last column and the ragged last row."""
+    case = WorkListCase("form1")
+    case.scene.camera.spin(-30.0, -25.0)
+    return case
+
+
+def tile_work(oracle, scene, mat, sky, W, H, bounces, tile_step=1, tile_first=0):
+    """A stand-in for the tiles' times: the oracle's per-pixel work (traversals, BLAS inner nodes, triangle tests) summed per 8 x 8
+    tile, the tiles of one rank of a row partition in their local order."""
+    w = oracle.tri_work_px(scene.pack_params(bounces), tri_buffers(scene, mat), sky.faces, W, H).astype(np.int64)
+    px = 16 * w[..., 0] + w[..., 1] + w[..., 2]
+    gx, gy = (W + 7) // 8, (H + 7) // 8
+    pad = np.zeros((gy * 8, gx * 8), np.int64)
+    pad[:H, :W] = px
+    tiles = pad.reshape(gy, 8, gx, 8).sum(axis=(1, 3))
+    return tiles[tile_first::tile_step].ravel()

@@ -2,40 +2,17 @@
 into 128 global bins, the last workgroup to finish turns them into split counts and first positions -- and order_scatter -- one
 global atomic per class and workgroup, then every tile placed), run on cost arrays of their own through the diagnostic entry point
 rt_order_tiles: the list must be a permutation, classes must not increase along it, and the two header words must be what the
-rule says (restated here in Python: quarter-octave classes, half / twice the throughput time, the caps)."""
+rule says (restated in Python in tests/helpers.py: quarter-octave classes, half / twice the throughput time, the caps)."""
 import ctypes
 
 import numpy as np
 import pytest
 
 from compute_raytracer_amd import abi
+from helpers import model
 
 pytestmark = pytest.mark.gpu
 U32 = ctypes.POINTER(ctypes.c_uint32)
-
-
-def cost_class(c):
-    c = int(c)
-    if c < 4:
-        return c
-    e = c.bit_length() - 1
-    return 4 * e + ((c >> (e - 2)) & 3) - 4
-
-
-def model(cost, wave_slots, mult4=1, mult16=4, cap16=64):
-    n = len(cost)
-    cls = np.array([cost_class(c) for c in cost])
-    total = int(np.asarray(cost, np.uint64).sum())
-    thr = total // (2 * max(wave_slots, 1))
-    cls_of = lambda v: cost_class(min(v, 0xFFFFFFFF))
-    above = lambda k: int((cls > k).sum())
-    split, split16 = above(cls_of(mult4 * thr)), above(cls_of(mult16 * thr))
-    if above(cls_of(4 * thr)) == 0:
-        split = split16 = 0
-    most, most16 = min(n // 16, 1024), min(n // 64, cap16)
-    split16 = min(split16, most16)
-    split = max(min(split, most), split16)
-    return split - split16, split16, cls
 
 
 def run(cost, wave_slots=5120):

@@ -10,16 +10,9 @@ import pytest
 import compute_raytracer_amd as rt
 from compute_raytracer_amd import abi
 from compute_raytracer_amd.scene_raytracing import CONSTANT_SKY_RGBA
-from helpers import diff_stats, gpu_render_tri, tri_buffers, triangle_scene
+from helpers import deepen_top_level, diff_stats, expected_form, gpu_render_tri, leafy_scene, random_sky, spine_scene, tri_buffers, triangle_scene
 
 pytestmark = pytest.mark.gpu
-
-
-def random_sky(seed, w=8, h=8):
-    rng = np.random.default_rng(seed)
-    m = rt.CubemapMaterial()
-    m.faces = [rng.integers(0, 256, (h, w, 4), dtype=np.uint8) for _ in range(6)]
-    return m
 
 
 # the kernels of the triangle path: 0 = the library's choice, one workgroup per tile over the relinked pair records
@@ -257,40 +250,6 @@ def test_scenes_beyond_the_packed_stack_take_the_index_stack(oracle, heatmap):
     assert np.array_equal(img, ref), diff_stats(img, ref)
 
 
-def spine_scene(depth):
-    """A BLAS no builder would make: a spine of `depth` inner nodes, each with a leaf as its FARTHER child, so that the
-    walk pushes one entry per level -- beyond the eight slots the persistent kernel keeps in LDS, and beyond the twenty the
-    reference's stack has at all (RK:71; RK:303-306 pushes without a guard: the index clamps to the last slot, and the pops
-    that follow read that slot again and again).  One triangle per leaf, each covering its own part of the view."""
-    base = 1                                                    # tlasNodesMax of one instance
-    nodes = np.zeros((1 + 2 * depth, 8), np.float32)            # S_0, then the pairs (A_k, S_{k+1}); the last "S" is a leaf
-    tris = np.zeros((depth + 1, 40), np.float32)
-    def box(i, lo, hi, left, count):
-        nodes[i, 0:3] = lo; nodes[i, 3] = left; nodes[i, 4:7] = hi; nodes[i, 7] = count
-    box(0, [-9, -9, -1.0], [9, 9, 5.0], base + 1, 0)
-    for k in range(depth):
-        a, s = 1 + 2 * k, 2 + 2 * k
-        box(a, [-9, -9, -3.0], [9, 9, -2.0], k, 1)                                   # leaf A_k: lookup slot k
-        if k + 1 < depth: box(s, [-9, -9, -1.0], [9, 9, 5.0], base + s + 1, 0)       # S_{k+1}
-        else: box(s, [-9, -9, -1.0], [9, 9, 5.0], depth, 1)                          # the bottom: a leaf inside the near box
-    for k in range(depth + 1):
-        z = -2.05 - 0.9 * k / depth if k < depth else -0.5
-        x0 = -8.0 + 16.0 * ((k * 7) % (depth + 1)) / (depth + 1)
-        w = 3.0 if k < depth else 40.0
-        # front face towards +z (RK:359 culls det < 1e-5)
-        for c, (x, y) in enumerate([(x0, -8.0), (x0 + w, -8.0), (x0 + w / 2, 9.0)]):
-            tris[k, 12 * c:12 * c + 3] = [x, y, z]
-            tris[k, 12 * c + 4:12 * c + 7] = [0, 0, 1]
-            tris[k, 12 * c + 8:12 * c + 10] = [c / 2.0, c % 2]
-        tris[k, 36:40] = [0.2 + 0.8 * ((k * 5) % 7) / 7.0, 0.3 + 0.7 * ((k * 3) % 5) / 5.0, 0.9 - 0.6 * (k % 4) / 4.0, 1.0 if k % 3 else 0.5]
-    d = dict(triangles=tris, blas_nodes=nodes, tri_lookup=np.arange(depth + 1, dtype=np.float32),
-             mesh_root=np.array([base]), mesh_box_lo=np.array([[-9.0, -9.0, -3.0]]), mesh_box_hi=np.array([[9.0, 9.0, 5.0]]),
-             inst_mesh=np.array([0]), inst_position=np.array([[0.0, 0.0, 0.0]]), inst_eulers=np.array([[0.0, 0.0, 0.0]]),
-             inst_speed=np.array([[0.0, 0.0, 0.0]]), camera_position=np.array([0.0593, 2.692, 3.293]),
-             camera_eulers=np.array([0.0, 106.0, 270.0], np.float32), light=np.array([0.0, 5.0, 6.0, 3.0, 0.3]))
-    return rt.SceneRaytracing.from_packed(d)
-
-
 @pytest.mark.parametrize("variant", [0, 6])
 @pytest.mark.parametrize("depth", [7, 12, 19, 20, 21, 33])
 def test_stack_depth_beyond_the_lds_slots_and_beyond_the_reference_stack(oracle, depth, variant):
@@ -312,36 +271,7 @@ def test_leaves_of_more_triangles_than_a_two_byte_stack_entry_counts(oracle, per
     per leaf take the four-byte entries (rt_api.hip: p16_ok); same frame either way."""
     wild = per_leaf < 0                                          # -3: three per leaf, and one leaf whose first slot lies far beyond the lookup
     per_leaf = abs(per_leaf)                                     # table (the oracle clamps it to the last slot; 14 bits would wrap it)
-    depth = 9                                                    # spine_scene's tree with `per_leaf` triangles in every leaf, side by side
-    nodes = np.zeros((1 + 2 * depth, 8), np.float32)
-    tris = np.zeros(((depth + 1) * per_leaf, 40), np.float32)
-    def box(i, lo, hi, left, count):
-        nodes[i, 0:3] = lo; nodes[i, 3] = left; nodes[i, 4:7] = hi; nodes[i, 7] = count
-    box(0, [-9, -9, -1.0], [9, 9, 5.0], 2, 0)
-    for k in range(depth):
-        a, sidx = 1 + 2 * k, 2 + 2 * k
-        box(a, [-9, -9, -3.0], [9, 9, -2.0], k * per_leaf, per_leaf)
-        if k + 1 < depth: box(sidx, [-9, -9, -1.0], [9, 9, 5.0], 1 + sidx + 1, 0)
-        else: box(sidx, [-9, -9, -1.0], [9, 9, 5.0], depth * per_leaf, per_leaf)
-    for k in range(depth + 1):
-        for j in range(per_leaf):
-            z = (-2.05 - 0.9 * k / depth if k < depth else -0.5) - 0.01 * j
-            x0 = -8.0 + 16.0 * ((k * 7) % (depth + 1)) / (depth + 1) + 0.7 * j
-            w = 2.0 if k < depth else 30.0
-            t = k * per_leaf + j
-            for c, (x, y) in enumerate([(x0, -8.0), (x0 + w, -8.0), (x0 + w / 2, 9.0)]):
-                tris[t, 12 * c:12 * c + 3] = [x, y, z]
-                tris[t, 12 * c + 4:12 * c + 7] = [0, 0, 1]
-                tris[t, 12 * c + 8:12 * c + 10] = [c / 2.0, c % 2]
-            tris[t, 36:40] = [0.2 + 0.8 * ((t * 5) % 7) / 7.0, 0.3 + 0.7 * ((t * 3) % 5) / 5.0, 0.9 - 0.6 * (t % 4) / 4.0, 1.0 if t % 3 else 0.5]
-    if wild:
-        nodes[5, 3] = 30000.0
-    dd = dict(triangles=tris, blas_nodes=nodes, tri_lookup=np.arange(tris.shape[0], dtype=np.float32),
-              mesh_root=np.array([1]), mesh_box_lo=np.array([[-9.0, -9.0, -3.0]]), mesh_box_hi=np.array([[9.0, 9.0, 5.0]]),
-              inst_mesh=np.array([0]), inst_position=np.array([[0.0, 0.0, 0.0]]), inst_eulers=np.array([[0.0, 0.0, 0.0]]),
-              inst_speed=np.array([[0.0, 0.0, 0.0]]), camera_position=np.array([0.0593, 2.692, 3.293]),
-              camera_eulers=np.array([0.0, 106.0, 270.0], np.float32), light=np.array([0.0, 5.0, 6.0, 3.0, 0.3]))
-    scene = rt.SceneRaytracing.from_packed(dd)
+    scene = leafy_scene(per_leaf, wild)
     mat = rt.Material(np.random.default_rng(per_leaf).integers(0, 256, (8, 8, 4), dtype=np.uint8))
     sky = random_sky(per_leaf)
     W, H, B = 160, 96, 3
@@ -378,53 +308,6 @@ def test_an_instance_that_changes_its_mesh_rebuilds_the_relinked_copy(oracle, va
         assert r.stats()["pair_rebuilds"] == (2 if variant == 0 else 0)
     finally:
         r.close()
-
-
-def deepen_top_level(scene, levels):
-    """The frame's top-level tree under `levels` extra inner nodes: each new node has the old tree (one level down) as its first
-    child and a leaf far away from everything (instance 0 again: never entered) as its second.  Same picture, a deeper walk."""
-    t = np.asarray(scene.frame["tlas_nodes"], np.float32).reshape(-1, 8)
-    n_old, extra = t.shape[0], 2 * levels
-    assert n_old + extra <= scene.tlasNodesMax
-    out = np.zeros((n_old + extra, 8), np.float32)
-    for k in range(levels):                                  # node 0 and the chain nodes at 1, 3, 5, ...: children at (2k+1, 2k+2)
-        i = 0 if k == 0 else 2 * k - 1
-        out[i] = [-1e4, -1e4, -1e4, 2 * k + 1, 1e4, 1e4, 1e4, 0]
-        out[2 * k + 2] = [9e3, 9e3, 9e3, 0, 9.1e3, 9.1e3, 9.1e3, 1]      # the far leaf
-    base = 2 * levels - 1                                    # where the old root goes; the rest of the old tree behind the chain
-    remap = lambda i: base if i == 0 else extra + i
-    for i in range(n_old):
-        row = t[i].copy()
-        if row[7] == 0:
-            row[3] = remap(int(row[3]))                      # old children sit side by side at left, left + 1 (left >= 1)
-        out[remap(i)] = row
-    scene.frame["tlas_nodes"] = out
-
-
-def expected_form(scene, mat):
-    """rt_tlas_fit.h restated: the stack form the library must pick for the frame's top-level tree (tiny 2, small 1, neither 0)."""
-    nodes = tri_buffers(scene, mat)["nodes"]
-    n = len(nodes)
-    def u32f(f):
-        f = float(f)
-        return 0 if not f > 0.0 else (4294967295 if f >= 4294967040.0 else int(f))
-    def fits(max_depth, max_nodes):
-        todo = [(0, 0)]
-        while todo:
-            i, d = todo.pop()
-            i = min(i, n - 1)
-            if i >= max_nodes: return False
-            if u32f(nodes[i, 7]) != 0: continue
-            if d >= max_depth: return False
-            left = u32f(nodes[i, 3])
-            todo += [(left, d + 1), ((left + 1) & 0xFFFFFFFF, d + 1)]
-        return True
-    if len(scene.instances) > 16: return 0
-    if len(scene.instances) > 12: return 4 if fits(8, 32) else 0       # 13-16 instances: the form that stages sixteen records
-    if len(scene.instances) <= 4 and fits(3, 8): return 2
-    if fits(4, 16): return 1
-    if fits(8, 24): return 3
-    return 4 if fits(8, 32) else 0
 
 
 @pytest.mark.parametrize("n_models,deepen", [(1, 0), (3, 0), (3, 2), (4, 2), (11, 0), (11, 3), (11, 7), (14, 0), (15, 1)])
