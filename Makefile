@@ -7,7 +7,7 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-fast-math -Wall -Wn
 SRCS     := $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h)) include/rt355.h
 # identity of the build: profiles (profiles/traffic.json) are evidence for the sources they were taken with
 BUILD_ID := $(shell cat $(SRCS) | sha256sum | cut -c1-16)
-OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o
+OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o $(CSRC)/rt_query.o
 
 all: lib oracle node
 
@@ -22,6 +22,10 @@ $(CSRC)/rt_bvh.o: $(CSRC)/rt_bvh.hip $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(C
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/rt_triangles.o: $(CSRC)/rt_triangles.hip $(CSRC)/rt_tri_device.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
+
+# ray queries: the triangle kernel's traversal and the literal sphere test, the same flags (exactness rests on them)
+$(CSRC)/rt_query.o: $(CSRC)/rt_query.hip $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/rt_assemble.o: $(CSRC)/rt_assemble.hip $(CSRC)/rt_types.h include/rt355.h

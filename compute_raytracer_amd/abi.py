@@ -34,6 +34,7 @@ SYMBOLS = [
     "rt_group_create", "rt_group_destroy", "rt_group_size", "rt_group_ctx", "rt_group_render", "rt_group_wait",
     "rt_build_id", "rt_kernel_name", "rt_set_comm_timeout",
     "rt_read_pixels_async", "rt_read_pixels_wait", "rt_host_alloc", "rt_host_free",
+    "rt_trace_rays", "rt_trace_rays_host", "rt_pick",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -51,6 +52,18 @@ class RtStats(ctypes.Structure):
         ("kernel_id", ctypes.c_uint32), ("grid_share", ctypes.c_uint32), ("instance_uploads", ctypes.c_uint32),
         ("tri_form", ctypes.c_uint32), ("pair_rebuilds", ctypes.c_uint32),
     ]
+
+
+class RtHit(ctypes.Structure):
+    """rt_hit (include/rt355.h): the nearest hit of one ray, 32 bytes."""
+    _fields_ = [
+        ("t", ctypes.c_float), ("u", ctypes.c_float), ("v", ctypes.c_float),
+        ("prim", ctypes.c_int32), ("instance", ctypes.c_int32), ("normal", ctypes.c_float * 3),
+    ]
+
+
+# the same record as a numpy dtype: an (n,) array of it is what rt_trace_rays_host / rt_pick fill
+HIT_DTYPE = [("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("instance", "<i4"), ("normal", "<f4", (3,))]
 
 
 class RtError(RuntimeError):
@@ -147,6 +160,9 @@ def load():
         "rt_read_pixels_wait": (ctypes.c_int, [vp]),
         "rt_host_alloc": (ctypes.c_int, [sz, ctypes.POINTER(vp)]),
         "rt_host_free": (ctypes.c_int, [vp]),
+        "rt_trace_rays": (ctypes.c_int, [vp, vp, u32, vp, vp]),
+        "rt_trace_rays_host": (ctypes.c_int, [vp, vp, u32, vp]),
+        "rt_pick": (ctypes.c_int, [vp, vp, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -256,6 +256,9 @@ int rt_destroy(rt_ctx* c) {
     for (uint32_t i = 0; i < c->in_flight; ++i) (void)hipEventSynchronize(c->ev_done[i]);
     for (int k = 0; k < kStreams; ++k)
         if (c->streams[k]) (void)hipStreamSynchronize(c->streams[k]);
+    if (c->query_pending) (void)hipEventSynchronize(c->ev_query);
+    if (c->query_stream) { (void)hipStreamSynchronize(c->query_stream); (void)hipStreamDestroy(c->query_stream); }
+    if (c->ev_query) (void)hipEventDestroy(c->ev_query);
     if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     for (int k = 0; k < kStreams; ++k)
         if (c->ev_copy[k]) (void)hipEventDestroy(c->ev_copy[k]);
@@ -270,7 +273,8 @@ int rt_destroy(rt_ctx* c) {
     (void)hipFree(c->d_queue);
     (void)hipFree(c->d_bvh_rec);
     (void)hipFree(c->d_bvh_link);
-    for (rt_ctx::DevBuf* b : {&c->d_tri, &c->d_tri_lookup, &c->d_tex, &c->d_corners, &c->d_flow}) (void)hipFree(b->p);
+    for (rt_ctx::DevBuf* b : {&c->d_tri, &c->d_tri_lookup, &c->d_tex, &c->d_corners, &c->d_flow, &c->d_qrays, &c->d_qhits, &c->d_qxy})
+        (void)hipFree(b->p);
     for (int k = 0; k < kStreams; ++k) { (void)hipFree(c->d_tile_cost[k].p); (void)hipFree(c->d_tile_order[k].p); }
     for (int v = 0; v < kVersions; ++v)
         for (rt_ctx::DevBuf* b : {&c->d_nodes[v], &c->d_blas[v], &c->d_blas_lookup[v]}) (void)hipFree(b->p);
@@ -309,6 +313,11 @@ uint32_t rt_padded_tiles(uint32_t height, uint32_t world) {
 
 // Scene-setup calls change device state that frames in flight may read: they drain first.
 int rt_drain(rt_ctx* c) {
+    if (c->query_pending) {         // a ray query reads the scene too (rt_trace_rays)
+        RT_HIP(hipEventSynchronize(c->ev_query));
+        c->query_pending = false;
+        c->query_versions = false;
+    }
     bool copies = false;
     for (int k = 0; k < kStreams; ++k) copies = copies || c->copy_pending[k];
     if (copies) { int rc = rt_read_pixels_wait(c); if (rc != RT_OK) return rc; }
@@ -624,6 +633,125 @@ int rt_set_variant(rt_ctx* c, int variant) {
     return RT_OK;
 }
 
+// ---- the triangle scene a kernel reads: one place for frames (rt_enqueue) and ray queries (rt_trace_rays) ----
+
+// The compact corner array follows the triangles and the lookup table: built on `s` by the first frame or query that needs it
+// after rt_write_triangles / rt_write_tri_lookup -- BEFORE a frame takes a slot of the event ring (it may drain the frames in
+// flight, which empties the ring).
+static int ensure_corners(rt_ctx* c, hipStream_t s) {
+    if (c->corners_valid) return RT_OK;
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    const uint32_t n_slots = (uint32_t)(c->d_tri_lookup.used / 4u);
+    { int rc = grow_buf(c, c->d_corners, (size_t)n_slots * 48u); if (rc != RT_OK) return rc; }
+    if (c->scene_stream && c->scene_stream != s) RT_HIP(hipStreamWaitEvent(s, c->ev_scene, 0));
+    RT_HIP(rt_launch_tri_corners(static_cast<float4*>(c->d_corners.p), static_cast<const float*>(c->d_tri.p),
+                                 static_cast<const float*>(c->d_tri_lookup.p), n_slots, (uint32_t)(c->d_tri.used / 160u), s));
+    RT_HIP(hipEventRecord(c->ev_scene, s));          // frames on other streams wait for it (the scene-update event)
+    c->scene_stream = s;
+    c->corners_valid = true;
+    return RT_OK;
+}
+
+// The instance roots of a scene whose instance data travels with the frame (up to 16 instances) and whose indices fit the relinked
+// pair records (rt_flow_build.h); false when the scene does not fit them.
+static bool tri_pair_roots(const rt_ctx* c, uint32_t (&roots)[kInstMax], uint32_t& n_inst) {
+    const uint32_t n_nodes = (uint32_t)(c->nodes_used / 32u);
+    n_inst = (uint32_t)(c->inst.blas.size() / 20u);
+    const bool fits = c->inst.blas_on && c->inst.lookup_on && n_inst >= 1u && n_inst <= kInstMax && !c->inst.lookup.empty() &&
+                      c->inst.lookup.size() <= kInstMax && n_nodes >= 1u && n_nodes <= 65536u && c->d_tri_lookup.used / 4u <= 65536u &&
+                      c->node_count_max <= 65535u && c->h_nodes.size() / 8u >= n_nodes;
+    if (!fits) return false;
+    for (uint32_t i = 0; i < n_inst; ++i) roots[i] = rt_flow_u32f(c->inst.blas[20u * i + 16u]);
+    return true;
+}
+
+// The relinked copy is usable: current (no write has reached it, the same node count) and knowing every root -- and then the
+// roots' metas.  Never rebuilds it (a frame does, rt_enqueue).
+static bool tri_pairs_current(const rt_ctx* c, const uint32_t* roots, uint32_t n_inst, uint32_t (&root_meta)[kInstMax]) {
+    const uint32_t n_nodes = (uint32_t)(c->nodes_used / 32u);
+    const bool ok = !c->flow_dirty && c->flow.ok && c->flow.n_pairs != 0u && c->flow.n_nodes == n_nodes && rt_flow_covers(c->flow, roots, n_inst);
+    if (ok) {
+        const uint32_t last = n_nodes - 1u;
+        for (uint32_t i = 0; i < n_inst; ++i)
+            root_meta[i] = rt_flow_meta(c->h_nodes.data(), n_nodes, roots[i] < last ? roots[i] : last, c->flow.pair_of);
+    }
+    return ok;
+}
+
+// The scene over version `v` of the per-frame buffers (the static part of the scene is in every version), with the relinked pair
+// records where `have_pairs` says they are current.  Work list, debug and form fields are the caller's.
+static void tri_scene(const rt_ctx* c, uint32_t v, bool have_pairs, const uint32_t (&root_meta)[kInstMax], RtTriScene& ts) {
+    ts.nodes = static_cast<const float4*>(c->d_nodes[v].p);
+    ts.blas = static_cast<const float*>(c->d_blas[v].p);
+    ts.tri = static_cast<const float*>(c->d_tri.p);
+    ts.corners = static_cast<const float4*>(c->d_corners.p);
+    ts.tri_lookup = static_cast<const float*>(c->d_tri_lookup.p);
+    ts.blas_lookup = static_cast<const float*>(c->d_blas_lookup[v].p);
+    ts.tex = static_cast<const uint8_t*>(c->d_tex.p);
+    ts.n_nodes = (uint32_t)(c->nodes_used / 32u);
+    ts.n_blas = c->inst.blas_on ? (uint32_t)(c->inst.blas.size() / 20u) : (uint32_t)(c->d_blas[v].used / 80u);
+    ts.n_tri = (uint32_t)(c->d_tri.used / 160u);
+    ts.n_tri_lookup = (uint32_t)(c->d_tri_lookup.used / 4u);
+    ts.n_blas_lookup = c->inst.lookup_on ? (uint32_t)c->inst.lookup.size() : (uint32_t)(c->d_blas_lookup[v].used / 4u);
+    ts.tex_w = c->tex_w; ts.tex_h = c->tex_h;
+    ts.packed_ok = (c->node_count_max <= 65535u && ts.n_nodes <= 65536u && ts.n_tri_lookup <= 65536u) ? 1u : 0u;
+    // the top-level tree this frame walks (the mirror holds every node write, per-frame heads included): small enough for the
+    // four-slot TLAS stack?  (rt_tlas_fit.h; the same constants as the kernel's: rt_tri_device.h kSmallStack / kSmallNodes)
+    ts.tlas_small = 0u;
+    if (c->h_nodes.size() / 8u >= ts.n_nodes) {
+        if (ts.n_blas <= 4u && rt_tlas_fits(c->h_nodes.data(), ts.n_nodes, 3u, 8u)) ts.tlas_small = 2u;
+        else if (rt_tlas_fits(c->h_nodes.data(), ts.n_nodes, 4u, 16u)) ts.tlas_small = 1u;
+        else if (rt_tlas_fits(c->h_nodes.data(), ts.n_nodes, 8u, 24u)) ts.tlas_small = 3u;
+        else if (rt_tlas_fits(c->h_nodes.data(), ts.n_nodes, 8u, 32u)) ts.tlas_small = 4u;
+    }
+    // two-byte stack entries (count << 14 | x): every meta of the records and of this frame's roots must fit them
+    ts.p16_ok = (have_pairs && c->flow.max_count <= 3u && c->flow.max_x <= 16383u) ? 1u : 0u;
+    for (uint32_t i = 0; i < kInstMax && ts.p16_ok; ++i)
+        if ((root_meta[i] >> 16) > 3u || (root_meta[i] & 0xFFFFu) > 16383u) ts.p16_ok = 0u;
+    // (13-16 instances: only the form that stages sixteen records can walk the pair records -- the others find a root's meta in
+    // one of TWELVE staged records --, i.e. only a frame whose tree passed a walk above)
+    ts.pairs = (have_pairs && (ts.n_blas <= 12u || ts.tlas_small != 0u)) ? static_cast<const float4*>(c->d_flow.p) : nullptr;
+    for (uint32_t i = 0; i < kInstMax; ++i) ts.root_meta[i] = root_meta[i];
+}
+
+// The instance data that travels with a frame (inst.blas_on / lookup_on), by value, in the layout the small forms stage it in
+// (rt_tri_types.h: RtTriInst): the head of the node buffer from the mirror, the records with the lookup entries and the roots'
+// metas (ts.root_meta) in their padding words.
+static void tri_fill_inst(const rt_ctx* c, RtTriScene& ts) {
+    const uint32_t nn = std::min(ts.n_nodes, kInstHeadNodes), nb = std::min(ts.n_blas, kInstBlas);
+    std::memcpy(ts.inst.head, c->h_nodes.data(), (size_t)nn * 32u);
+    std::memcpy(ts.inst.blas, c->inst.blas.data(), (size_t)nb * 80u);
+    const uint32_t nl = std::min(ts.n_blas_lookup, nb);
+    for (uint32_t k = 0; k < nb; ++k) {
+        if (k < nl) ts.inst.blas[20u * k + 19u] = c->inst.lookup[k];
+        std::memcpy(&ts.inst.blas[20u * k + 17u], &ts.root_meta[k], 4);
+    }
+}
+
+// Brings version `v` of the per-frame buffers to the host's current instance state (a one-workgroup kernel on `s` whose kernarg
+// block holds the values).  Every frame among the first `slot` of the event ring that reads the version must be through first,
+// and so must the latest ray query that read a version.
+static int apply_version(rt_ctx* c, uint32_t v, uint32_t slot, hipStream_t s) {
+    for (uint32_t i = v; i < slot; i += (uint32_t)kVersions) RT_HIP(hipStreamWaitEvent(s, c->ev_k1[i], 0));
+    if (c->query_versions && c->ev_query) RT_HIP(hipStreamWaitEvent(s, c->ev_query, 0));
+    RtInstanceArgs ia;
+    ia.nodes = static_cast<float*>(c->d_nodes[v].p);
+    ia.blas = static_cast<float*>(c->d_blas[v].p);
+    ia.lookup = static_cast<float*>(c->d_blas_lookup[v].p);
+    ia.n_head_f = ia.nodes ? c->inst.head_nodes * 8u : 0u;
+    ia.n_blas_f = (c->inst.blas_on && ia.blas) ? (uint32_t)c->inst.blas.size() : 0u;
+    ia.n_lookup_f = (c->inst.lookup_on && ia.lookup) ? (uint32_t)c->inst.lookup.size() : 0u;
+    if (ia.n_head_f) std::memcpy(ia.data, c->inst.head.data(), ia.n_head_f * sizeof(float));
+    if (ia.n_blas_f) std::memcpy(ia.data + 31 * 8, c->inst.blas.data(), ia.n_blas_f * sizeof(float));
+    if (ia.n_lookup_f) std::memcpy(ia.data + 31 * 8 + 16 * 20, c->inst.lookup.data(), ia.n_lookup_f * sizeof(float));
+    RT_HIP(rt_launch_apply_instances(ia, s));
+    if (!c->ev_ver[v]) RT_HIP(hipEventCreateWithFlags(&c->ev_ver[v], hipEventDisableTiming));
+    RT_HIP(hipEventRecord(c->ev_ver[v], s));
+    c->ver_stream[v] = s;
+    c->ver_gen[v] = c->inst.gen;
+    return RT_OK;
+}
+
 int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     if (!c->W || !c->H) return fail(RT_ERR_STATE, "rt_render: rt_resize has not been called");
     if (!c->have_params) return fail(RT_ERR_STATE, "rt_render: rt_write_params has not been called");
@@ -714,18 +842,7 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     }
     // ---- what the triangle kernels read beside the reference's buffers: built here, BEFORE a slot of the event ring is
     // taken (both may have to drain the frames in flight, which empties the ring) ----
-    if (tri && !c->corners_valid) {
-        // the compact corner array follows the triangles and the lookup table
-        { int rc = drain(c); if (rc != RT_OK) return rc; }
-        const uint32_t n_slots = (uint32_t)(c->d_tri_lookup.used / 4u);
-        { int rc = grow_buf(c, c->d_corners, (size_t)n_slots * 48u); if (rc != RT_OK) return rc; }
-        if (c->scene_stream && c->scene_stream != s) RT_HIP(hipStreamWaitEvent(s, c->ev_scene, 0));
-        RT_HIP(rt_launch_tri_corners(static_cast<float4*>(c->d_corners.p), static_cast<const float*>(c->d_tri.p),
-                                     static_cast<const float*>(c->d_tri_lookup.p), n_slots, (uint32_t)(c->d_tri.used / 160u), s));
-        RT_HIP(hipEventRecord(c->ev_scene, s));          // frames on other streams wait for it (the scene-update event)
-        c->scene_stream = s;
-        c->corners_valid = true;
-    }
+    if (tri) { int rc = ensure_corners(c, s); if (rc != RT_OK) return rc; }
     // The relinked pair records of the BLAS trees (rt_flow_build.h), for scenes whose instance data travels with the frame (up
     // to 16 instances) and whose indices fit 16 bits: rebuilt when a write has reached the nodes the copy was made from or a
     // frame names a root it does not know -- from the union of the roots it knows and the new ones, so that a host that
@@ -734,13 +851,8 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     bool have_pairs = false;       // the relinked copy is current and covers this frame's roots
     if (tri && c->kernel != RT_KERNEL_HEATMAP && c->variant != 6) {
         const uint32_t n_nodes = (uint32_t)(c->nodes_used / 32u);
-        const uint32_t n_inst = (uint32_t)(c->inst.blas.size() / 20u);
-        const bool fits = c->inst.blas_on && c->inst.lookup_on && n_inst >= 1u && n_inst <= kInstMax && !c->inst.lookup.empty() &&
-                          c->inst.lookup.size() <= kInstMax && n_nodes >= 1u && n_nodes <= 65536u && c->d_tri_lookup.used / 4u <= 65536u &&
-                          c->node_count_max <= 65535u && c->h_nodes.size() / 8u >= n_nodes;
-        if (fits) {
-            uint32_t roots[kInstMax];
-            for (uint32_t i = 0; i < n_inst; ++i) roots[i] = rt_flow_u32f(c->inst.blas[20u * i + 16u]);
+        uint32_t roots[kInstMax], n_inst = 0;
+        if (tri_pair_roots(c, roots, n_inst)) {
             // (the per-frame head of the node buffer lives in inst.head until a frame carries it: the mirror has it already)
             const bool stale = c->flow_dirty || c->flow.n_nodes != n_nodes;
             const bool need = stale || !rt_flow_covers(c->flow, roots, n_inst);
@@ -766,13 +878,7 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
                     if (rc != RT_OK) return rc;
                 }
             }
-            // usable: current (no write has reached it, the same node count) and knowing every root of this frame
-            have_pairs = !c->flow_dirty && c->flow.ok && c->flow.n_pairs != 0u && c->flow.n_nodes == n_nodes && rt_flow_covers(c->flow, roots, n_inst);
-            if (have_pairs) {
-                const uint32_t last = n_nodes - 1u;
-                for (uint32_t i = 0; i < n_inst; ++i)
-                    root_meta[i] = rt_flow_meta(c->h_nodes.data(), n_nodes, roots[i] < last ? roots[i] : last, c->flow.pair_of);
-            }
+            have_pairs = tri_pairs_current(c, roots, n_inst, root_meta);
         }
     }
     if (c->in_flight == RT355_MAX_IN_FLIGHT) {   // event ring full: drain
@@ -883,50 +989,13 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     RtTriScene ts;
     std::memset(&ts, 0, sizeof ts);
     if (tri) {
-        ts.nodes = static_cast<const float4*>(c->d_nodes[v].p);
-        ts.blas = static_cast<const float*>(c->d_blas[v].p);
-        ts.tri = static_cast<const float*>(c->d_tri.p);
-        ts.corners = static_cast<const float4*>(c->d_corners.p);
-        ts.tri_lookup = static_cast<const float*>(c->d_tri_lookup.p);
-        ts.blas_lookup = static_cast<const float*>(c->d_blas_lookup[v].p);
-        ts.tex = static_cast<const uint8_t*>(c->d_tex.p);
-        ts.n_nodes = (uint32_t)(c->nodes_used / 32u);
-        ts.n_blas = c->inst.blas_on ? (uint32_t)(c->inst.blas.size() / 20u) : (uint32_t)(c->d_blas[v].used / 80u);
-        ts.n_tri = (uint32_t)(c->d_tri.used / 160u);
-        ts.n_tri_lookup = (uint32_t)(c->d_tri_lookup.used / 4u);
-        ts.n_blas_lookup = c->inst.lookup_on ? (uint32_t)c->inst.lookup.size() : (uint32_t)(c->d_blas_lookup[v].used / 4u);
-        ts.tex_w = c->tex_w; ts.tex_h = c->tex_h;
-        ts.packed_ok = (c->node_count_max <= 65535u && ts.n_nodes <= 65536u && ts.n_tri_lookup <= 65536u) ? 1u : 0u;
+        tri_scene(c, v, have_pairs, root_meta, ts);
         ts.tile_order = nullptr; ts.tile_cost = nullptr; ts.xcd_rows = 0u; ts.prio = 0u; ts.in_flight = hint ? 1u : 0u; ts.dbg = nullptr;
-        // the top-level tree this frame walks (the mirror holds every node write, per-frame heads included): small enough for the
-        // four-slot TLAS stack?  (rt_tlas_fit.h; the same constants as the kernel's: rt_tri_device.h kSmallStack / kSmallNodes)
-        ts.tlas_small = 0u;
-        if (c->h_nodes.size() / 8u >= ts.n_nodes) {
-            if (ts.n_blas <= 4u && rt_tlas_fits(c->h_nodes.data(), ts.n_nodes, 3u, 8u)) ts.tlas_small = 2u;
-            else if (rt_tlas_fits(c->h_nodes.data(), ts.n_nodes, 4u, 16u)) ts.tlas_small = 1u;
-            else if (rt_tlas_fits(c->h_nodes.data(), ts.n_nodes, 8u, 24u)) ts.tlas_small = 3u;
-            else if (rt_tlas_fits(c->h_nodes.data(), ts.n_nodes, 8u, 32u)) ts.tlas_small = 4u;
-        }
-        // two-byte stack entries (count << 14 | x): every meta of the records and of this frame's roots must fit them
-        ts.p16_ok = (have_pairs && c->flow.max_count <= 3u && c->flow.max_x <= 16383u) ? 1u : 0u;
-        for (uint32_t i = 0; i < kInstMax && ts.p16_ok; ++i)
-            if ((root_meta[i] >> 16) > 3u || (root_meta[i] & 0xFFFFu) > 16383u) ts.p16_ok = 0u;
-        // (13-16 instances: only the form that stages sixteen records can walk the pair records -- the others find a root's meta in
-        // one of TWELVE staged records --, i.e. only a frame whose tree passed a walk above)
-        ts.pairs = (have_pairs && (ts.n_blas <= 12u || ts.tlas_small != 0u)) ? static_cast<const float4*>(c->d_flow.p) : nullptr;
-        for (uint32_t i = 0; i < kInstMax; ++i) ts.root_meta[i] = root_meta[i];
         // which form of the kernel renders the frame (rt_triangles.hip); the small forms take the frame's instance data in their
         // own arguments, in the layout they stage it in
         ts.form = (uint32_t)rt_tri_stack_form(ts, c->kernel == RT_KERNEL_HEATMAP);
         if (ts.form != 0u) {
-            const uint32_t nn = std::min(ts.n_nodes, kInstHeadNodes), nb = std::min(ts.n_blas, kInstBlas);
-            std::memcpy(ts.inst.head, c->h_nodes.data(), (size_t)nn * 32u);
-            std::memcpy(ts.inst.blas, c->inst.blas.data(), (size_t)nb * 80u);
-            const uint32_t nl = std::min(ts.n_blas_lookup, nb);
-            for (uint32_t k = 0; k < nb; ++k) {
-                if (k < nl) ts.inst.blas[20u * k + 19u] = c->inst.lookup[k];
-                std::memcpy(&ts.inst.blas[20u * k + 17u], &root_meta[k], 4);
-            }
+            tri_fill_inst(c, ts);
             if (c->inst_gen_carried != c->inst.gen) { c->inst_gen_carried = c->inst.gen; ++c->stats.instance_uploads; }
         }
     }
@@ -940,22 +1009,7 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     // buffers: their instance data is in the kernel's own arguments, ts.inst above.  No kernel, no event, no wait; the versions
     // simply fall behind, and a later frame of another form brings its own up to date.)
     if (tri && ts.form == 0u && c->ver_gen[v] != c->inst.gen) {
-        for (uint32_t i = v; i < slot; i += (uint32_t)kVersions) RT_HIP(hipStreamWaitEvent(s, c->ev_k1[i], 0));
-        RtInstanceArgs ia;
-        ia.nodes = static_cast<float*>(c->d_nodes[v].p);
-        ia.blas = static_cast<float*>(c->d_blas[v].p);
-        ia.lookup = static_cast<float*>(c->d_blas_lookup[v].p);
-        ia.n_head_f = ia.nodes ? c->inst.head_nodes * 8u : 0u;
-        ia.n_blas_f = (c->inst.blas_on && ia.blas) ? (uint32_t)c->inst.blas.size() : 0u;
-        ia.n_lookup_f = (c->inst.lookup_on && ia.lookup) ? (uint32_t)c->inst.lookup.size() : 0u;
-        if (ia.n_head_f) std::memcpy(ia.data, c->inst.head.data(), ia.n_head_f * sizeof(float));
-        if (ia.n_blas_f) std::memcpy(ia.data + 31 * 8, c->inst.blas.data(), ia.n_blas_f * sizeof(float));
-        if (ia.n_lookup_f) std::memcpy(ia.data + 31 * 8 + 16 * 20, c->inst.lookup.data(), ia.n_lookup_f * sizeof(float));
-        RT_HIP(rt_launch_apply_instances(ia, s));
-        if (!c->ev_ver[v]) RT_HIP(hipEventCreateWithFlags(&c->ev_ver[v], hipEventDisableTiming));
-        RT_HIP(hipEventRecord(c->ev_ver[v], s));
-        c->ver_stream[v] = s;
-        c->ver_gen[v] = c->inst.gen;
+        { int rc = apply_version(c, v, slot, s); if (rc != RT_OK) return rc; }
         ++c->stats.instance_uploads;
     } else if (tri && ts.form == 0u && c->ev_ver[v] && c->ver_stream[v] != s) {
         RT_HIP(hipStreamWaitEvent(s, c->ev_ver[v], 0));
@@ -1324,6 +1378,161 @@ int rt_filter_plan(const float* records, uint32_t n, const float params[24], int
     rt_plan((double)(float)rt_scene_bound(records, n), rt_scene_min_radius(records, n), params, ok, sgn);
     *filter_ok = ok ? 1 : 0;
     *signed_filter = (int)sgn;
+    return RT_OK;
+}
+
+// ---- ray queries (rt_query.hip) ------------------------------------------------------------------------------------------
+
+// What a query on `s` reads, and its order behind the last scene update.  Triangle scenes: `ts`, with the instance data in the
+// arguments (*inst = 1) when it travels with the frames -- the per-frame buffers then hold an older pose -- and otherwise from a
+// version of the per-frame buffers that holds the current state (every version, for instance sets written by write_versions).
+static int query_prepare(rt_ctx* c, const char* who, hipStream_t s, bool& tri, RtTriScene& ts, int& inst) {
+    char msg[160];
+    tri = c->scene_kind == 1;
+    inst = 0;
+    if (tri) {
+        const bool have_blas = c->inst.blas_on ? !c->inst.blas.empty() : c->d_blas[0].used != 0;
+        const bool have_lookup = c->inst.lookup_on ? !c->inst.lookup.empty() : c->d_blas_lookup[0].used != 0;
+        if (!c->d_tri.used || !c->nodes_used || !have_blas || !c->d_tri_lookup.used || !have_lookup) {
+            std::snprintf(msg, sizeof msg, "%s: a triangle scene needs rt_write_triangles, _nodes, _blas, _tri_lookup and _blas_lookup", who);
+            return fail(RT_ERR_STATE, msg);
+        }
+    } else if (!c->have_spheres) {
+        std::snprintf(msg, sizeof msg, "%s: no scene has been written", who);
+        return fail(RT_ERR_STATE, msg);
+    }
+    RT_HIP(hipSetDevice(c->device));
+    if (!c->ev_query) RT_HIP(hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
+    if (tri) { int rc = ensure_corners(c, s); if (rc != RT_OK) return rc; }
+    uint32_t v = 0;
+    uint32_t root_meta[kInstMax] = {0};
+    bool have_pairs = false;
+    if (tri) {
+        const uint32_t n_inst = (uint32_t)(c->inst.blas.size() / 20u);
+        // (a lookup table longer than the instance list names entries that are not staged: the versions then)
+        inst = (c->inst.blas_on && c->inst.lookup_on && n_inst >= 1u && c->inst.lookup.size() <= n_inst) ? 1 : 0;
+        if (inst) {
+            uint32_t roots[kInstMax], n_roots = 0;
+            if (tri_pair_roots(c, roots, n_roots)) have_pairs = tri_pairs_current(c, roots, n_roots, root_meta);
+        } else {
+            int cur = -1;
+            for (int k = 0; k < kVersions && cur < 0; ++k)
+                if (c->ver_gen[k] == c->inst.gen) cur = k;
+            if (cur < 0) {
+                // no version holds the current state (a per-frame write since the last frame of the twenty-slot form): bring one
+                // up to date -- with nothing in flight, as a frame of this scene after rt_write_blas / _blas_lookup of more than
+                // sixteen instances finds it (they drain)
+                { int rc = drain(c); if (rc != RT_OK) return rc; }
+                cur = 0;
+                { int rc = apply_version(c, 0u, 0u, s); if (rc != RT_OK) return rc; }
+            } else if (c->ev_ver[cur] && c->ver_stream[cur] != s) {
+                RT_HIP(hipStreamWaitEvent(s, c->ev_ver[cur], 0));
+            }
+            v = (uint32_t)cur;
+            c->query_versions = true;
+        }
+    }
+    if (c->scene_stream && c->scene_stream != s) RT_HIP(hipStreamWaitEvent(s, c->ev_scene, 0));
+    // queries on different streams run in order: ev_query then stands for all of them (rt_drain)
+    if (c->query_pending && c->query_last != s) RT_HIP(hipStreamWaitEvent(s, c->ev_query, 0));
+    if (tri) {
+        std::memset(&ts, 0, sizeof ts);
+        tri_scene(c, v, have_pairs, root_meta, ts);
+        if (inst) tri_fill_inst(c, ts);
+    }
+    return RT_OK;
+}
+
+static int query_launch(rt_ctx* c, const float4* rays, float4* hits, uint32_t n, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+    if (tri) RT_HIP(rt_launch_query_triangles(ts, inst, rays, hits, n, s));
+    else RT_HIP(rt_launch_query_spheres(c->d_records, c->n, rays, hits, n, s));
+    RT_HIP(hipEventRecord(c->ev_query, s));
+    c->query_pending = true;
+    c->query_last = s;
+    return RT_OK;
+}
+
+// a staging buffer of the host-memory queries (synchronous: idle between calls): grows, contents not kept
+static int grow_staging(rt_ctx::DevBuf& b, size_t need) {
+    if (need <= b.cap) return RT_OK;
+    (void)hipFree(b.p);
+    b.p = nullptr; b.cap = 0;
+    const size_t cap = std::max(need, (size_t)65536u);
+    RT_HIP(hipMalloc(&b.p, cap));
+    b.cap = cap;
+    return RT_OK;
+}
+
+static int query_stream(rt_ctx* c, hipStream_t& s) {
+    RT_HIP(hipSetDevice(c->device));
+    if (!c->query_stream) RT_HIP(hipStreamCreateWithFlags(&c->query_stream, hipStreamNonBlocking));
+    s = c->query_stream;
+    return RT_OK;
+}
+
+static_assert(sizeof(rt_hit) == 32, "rt_hit is two float4");
+
+int rt_trace_rays(rt_ctx* c, const float* rays, uint32_t n, rt_hit* hits, void* hip_stream) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_trace_rays: ctx is NULL");
+    if (n == 0) return RT_OK;
+    if (!rays || !hits) return fail(RT_ERR_INVALID_ARG, "rt_trace_rays: NULL argument");
+    if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) % 16u)
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_rays: rays and hits must be 16-byte aligned");
+    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_trace_rays", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    return query_launch(c, reinterpret_cast<const float4*>(rays), reinterpret_cast<float4*>(hits), n, s, tri, ts, inst);
+}
+
+int rt_trace_rays_host(rt_ctx* c, const float* rays, uint32_t n, rt_hit* hits) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_trace_rays_host: ctx is NULL");
+    if (n == 0) return RT_OK;
+    if (!rays || !hits) return fail(RT_ERR_INVALID_ARG, "rt_trace_rays_host: NULL argument");
+    hipStream_t s;
+    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_trace_rays_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    const size_t bytes = (size_t)n * 32u;
+    { int rc = grow_staging(c->d_qrays, bytes); if (rc != RT_OK) return rc; }
+    { int rc = grow_staging(c->d_qhits, bytes); if (rc != RT_OK) return rc; }
+    RT_HIP(hipMemcpyAsync(c->d_qrays.p, rays, bytes, hipMemcpyHostToDevice, s));
+    { int rc = query_launch(c, static_cast<const float4*>(c->d_qrays.p), static_cast<float4*>(c->d_qhits.p), n, s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    RT_HIP(hipMemcpyAsync(hits, c->d_qhits.p, bytes, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    return RT_OK;
+}
+
+int rt_pick(rt_ctx* c, const uint32_t* xy, uint32_t n, rt_hit* hits) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_pick: ctx is NULL");
+    if (n == 0) return RT_OK;
+    if (!xy || !hits) return fail(RT_ERR_INVALID_ARG, "rt_pick: NULL argument");
+    if (!c->W || !c->H) return fail(RT_ERR_STATE, "rt_pick: rt_resize has not been called");
+    if (!c->have_params) return fail(RT_ERR_STATE, "rt_pick: rt_write_params has not been called");
+    for (uint32_t i = 0; i < n; ++i)          // full-frame coordinates, whatever the partition
+        if (xy[2u * i] >= c->W || xy[2u * i + 1u] >= c->H) return fail(RT_ERR_INVALID_ARG, "rt_pick: pixel outside the frame");
+    hipStream_t s;
+    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_pick", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    const size_t bytes = (size_t)n * 32u;
+    { int rc = grow_staging(c->d_qxy, (size_t)n * 8u); if (rc != RT_OK) return rc; }
+    { int rc = grow_staging(c->d_qrays, bytes); if (rc != RT_OK) return rc; }
+    { int rc = grow_staging(c->d_qhits, bytes); if (rc != RT_OK) return rc; }
+    RT_HIP(hipMemcpyAsync(c->d_qxy.p, xy, (size_t)n * 8u, hipMemcpyHostToDevice, s));
+    RtFrameArgs fa;
+    std::memset(&fa, 0, sizeof fa);
+    std::memcpy(fa.p, c->params, sizeof fa.p);
+    fa.W = c->W; fa.H = c->H;
+    RT_HIP(rt_launch_pick_rays(fa, static_cast<const uint32_t*>(c->d_qxy.p), static_cast<float4*>(c->d_qrays.p), n, s));
+    { int rc = query_launch(c, static_cast<const float4*>(c->d_qrays.p), static_cast<float4*>(c->d_qhits.p), n, s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    RT_HIP(hipMemcpyAsync(hits, c->d_qhits.p, bytes, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
     return RT_OK;
 }
 

@@ -138,6 +138,14 @@ struct rt_ctx {
     uint32_t flow_frames_since = 0, flow_streak = 0, flow_cooldown = 0;   // frames since the last rebuild; consecutive frames that rebuilt; frames left on the node walk
     DevBuf d_flow;                               // the pair records
     DevBuf d_tri_dbg;                            // development builds: the triangle kernel's per-workgroup timeline
+    // Ray queries (rt_trace_rays_host / rt_pick): their own stream, staging buffers that grow as needed, and the event behind the
+    // latest query on any stream -- scene writes wait for it as they wait for the frames in flight (rt_drain)
+    hipStream_t query_stream = nullptr;
+    DevBuf d_qrays, d_qhits, d_qxy;
+    hipEvent_t ev_query = nullptr;
+    bool query_pending = false;
+    bool query_versions = false;         // ... and that query (or one before it since the last drain) read a version of the per-frame buffers
+    hipStream_t query_last = nullptr;    // the stream of that query
     uint32_t n_cus = 256;
     uint32_t tex_w = 0, tex_h = 0;
     int scene_kind = 0;                    // 0 spheres, 1 triangles: the primitive type written last

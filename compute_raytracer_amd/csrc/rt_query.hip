@@ -1,0 +1,158 @@
+// rt_query.hip -- ray queries on gfx950 (include/rt355.h: rt_trace_rays, rt_trace_rays_host, rt_pick): the nearest hit of
+// rays the caller supplies, against the scene the next frame would render.  Compiled like rt_triangles.hip with
+// -ffp-contract=off -fno-slp-vectorize: the traversal and the tests are the frame kernels' own device functions
+// (rt_tri_device.h, rt_filter.h), so a query's t, barycentrics and normal are bit for bit what the oracle computes for the
+// same ray (oracle/rt_oracle.c: rt_oracle_trace_tri_rays, hit_sphere).
+//
+// CDNA4 mapping: one ray per lane, wave64, kQueryWaves waves per workgroup.  A ray is two float4 {origin, -}, {dir, -} and a
+// hit two float4 {t, u, v, prim}, {instance, normal}: a wave reads and writes 2 KB in two coalesced 1 KB rows.
+//   query_triangles: traceTLAS (RK:168-244) with the twenty-slot top-level stack and the reference's guard, so that any
+//     top-level tree gives the oracle's answer; both stacks in LDS, slot-major as in trace_triangles.  The head of the
+//     top-level tree and the instance records are staged by stage_head -- from the kernel's arguments when the instance data
+//     travels with the frame (RtTriInst), from the per-frame buffers otherwise.
+//   query_spheres: the literal test (HK:307-331) over every sphere in index order, the records staged through LDS in chunks
+//     (any sphere count).  Not the bounding-sphere hierarchy: its no-lost-hit proof (rt_bvh.hip) assumes unit directions and
+//     origins within rt_plan's reach, and caller rays promise neither.
+//   pick_rays: the primary ray of pixel (x, y) (RK:76-86, rt_device.h: primary_dir) into a ray buffer.
+#include <type_traits>
+
+#include "rt_device.h"
+#include "rt_tri_types.h"
+#include "rt_tri_device.h"
+#include "rt_filter.h"
+
+namespace rtk {
+
+constexpr int kQueryWaves = 4;
+constexpr uint32_t kQueryThreads = 64u * kQueryWaves;
+constexpr uint32_t kSphereChunk = 1024u;       // sphere records {centre, radius^2} staged per round: 16 KB of LDS
+
+__device__ __forceinline__ void load_ray(const float4* __restrict__ rays, size_t i, v3& o, v3& d) {
+    const float4 a = rays[2u * i], b = rays[2u * i + 1u];
+    o = V(a.x, a.y, a.z);
+    d = V(b.x, b.y, b.z);
+}
+// rt_hit: {t, u, v, prim}, {instance, normal.xyz}
+__device__ __forceinline__ void store_hit(float4* __restrict__ hits, size_t i, float t, float u, float v, int prim, int inst, v3 n) {
+    hits[2u * i] = make_float4(t, u, v, __int_as_float(prim));
+    hits[2u * i + 1u] = make_float4(__int_as_float(inst), n.x, n.y, n.z);
+}
+__device__ __forceinline__ void store_miss(float4* __restrict__ hits, size_t i) {
+    store_hit(hits, i, -1.0f, 0.0f, 0.0f, -1, -1, V(0.0f, 0.0f, 0.0f));
+}
+
+// STK / PACKED / PAIRS / P16 as in trace_tlas; INST: the instance data came with the arguments (T.inst, stage_head<..., true>)
+template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
+__global__ __launch_bounds__(kQueryThreads) void query_triangles(const RtTriScene T, const float4* __restrict__ rays,
+                                                                 float4* __restrict__ hits, uint32_t n) {
+    typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
+    constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
+    __shared__ STK tstacks[kStack * kQueryThreads];
+    __shared__ BSTK bstacks[kStack * kQueryThreads];
+    __shared__ float4 s_nodes[2 * NODES];
+    __shared__ float s_blas[20 * BLAS];
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);   // (INST: roots in T.inst)
+    const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
+    if (i >= n) return;
+    v3 o, d;
+    load_ray(rays, i, o, d);
+    // A node buffer that lies wholly inside the head (RR's buffer for a scene of small meshes) was written as per-frame data: its
+    // BLAS nodes too are current only in the staged copy (the device versions are brought up to date by frames of the
+    // twenty-slot form alone) -- the node walk then reads them from LDS, through the generic address.
+    RtTriScene Tq = T;
+    if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
+    float traces = 0.0f;
+    const TriHit h = trace_tlas<false, STK, PACKED, PAIRS, P16>(Tq, L, o, d, tstacks + threadIdx.x, bstacks + threadIdx.x,
+                                                                 kQueryThreads, traces);
+    if (h.tri < 0) { store_miss(hits, i); return; }
+    // RK:334-338 for the winner (the staged record keeps the matrix in words 0-15)
+    const uint32_t bi = (uint32_t)h.blas;
+    const float* m = bi < L.n_blas ? L.blas + 20u * bi : T.blas + 20u * (size_t)bi;
+    const v3 nrm = hit_normal(T, h, m);
+    store_hit(hits, i, h.t, h.u, h.v, (int)tri_of(T, h.tri), h.blas, nrm);
+}
+
+// RK:311-322 over spheres with hitSphere (HK:307-331): tMin 0.001, the running nearest hit as tMax, the lowest index on a tie
+__global__ __launch_bounds__(kQueryThreads) void query_spheres(const float* __restrict__ records, uint32_t n_spheres,
+                                                               const float4* __restrict__ rays, float4* __restrict__ hits, uint32_t n) {
+    __shared__ float4 s_geo[kSphereChunk];
+    const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
+    const bool live = i < n;                       // every lane stages: no return before the last barrier
+    v3 o = V(0.0f, 0.0f, 0.0f), d = V(0.0f, 0.0f, 0.0f);
+    if (live) load_ray(rays, i, o, d);
+    const float a = dot(d, d);                     // HK:308
+    const float fa = 4.0f * a;                     // the (4*a) of HK:311
+    const float ta = 2.0f * a;                     // HK:317
+    float nearest = 9999.0f;                       // RK:172
+    int idx = -1;
+    for (uint32_t base = 0; base < n_spheres; base += kSphereChunk) {
+        const uint32_t m = n_spheres - base < kSphereChunk ? n_spheres - base : kSphereChunk;
+        __syncthreads();                           // the previous chunk is done with
+        for (uint32_t k = threadIdx.x; k < m; k += kQueryThreads) {
+            const float4* r = reinterpret_cast<const float4*>(records + 8u * ((size_t)base + k));
+            const float4 c = r[0], w = r[1];
+            s_geo[k] = make_float4(c.x, c.y, c.z, w.w * w.w);       // radius * radius (HK:310)
+        }
+        __syncthreads();
+        if (live) {
+            for (uint32_t k = 0; k < m; ++k) {
+                const float4 g = s_geo[k];
+                exact_full<false>(V(g.x, g.y, g.z), g.w, (int)(base + k), o, d, fa, ta, nearest, idx);
+            }
+        }
+    }
+    if (!live) return;
+    if (idx < 0) { store_miss(hits, i); return; }
+    const float* s = records + 8u * (size_t)idx;
+    const v3 position = add(o, scale(nearest, d));                     // HK:319
+    const v3 nrm = normalize(sub(position, V(s[0], s[1], s[2])));       // HK:320
+    store_hit(hits, i, nearest, 0.0f, 0.0f, idx, -1, nrm);
+}
+
+// the primary ray of pixel (x, y) (RK:76-86): the ray that pixel of the next frame starts with
+__global__ __launch_bounds__(256) void pick_rays(const RtFrameArgs A, const uint32_t* __restrict__ xy, float4* __restrict__ rays, uint32_t n) {
+    const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
+    if (i >= n) return;
+    const Scene sc = unpack_scene(A);
+    const v3 d = primary_dir(A, sc, xy[2u * i], xy[2u * i + 1u]);
+    rays[2u * i] = make_float4(sc.cameraPos.x, sc.cameraPos.y, sc.cameraPos.z, 0.0f);
+    rays[2u * i + 1u] = make_float4(d.x, d.y, d.z, 0.0f);
+}
+
+template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
+static void launch_qt(const RtTriScene& t, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)(((size_t)n + kQueryThreads - 1u) / kQueryThreads);
+    hipLaunchKernelGGL((query_triangles<STK, PACKED, PAIRS, P16, INST>), dim3(blocks), dim3(kQueryThreads), 0, s, t, rays, hits, n);
+}
+template <bool INST>
+static void launch_qt_walk(const RtTriScene& t, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
+    if (t.n_nodes <= 65536u && t.packed_ok) launch_qt<uint16_t, true, false, false, INST>(t, rays, hits, n, s);
+    else if (t.n_nodes <= 65536u)          launch_qt<uint16_t, false, false, false, INST>(t, rays, hits, n, s);
+    else                                   launch_qt<uint32_t, false, false, false, INST>(t, rays, hits, n, s);
+}
+
+}  // namespace rtk
+
+hipError_t rt_launch_query_triangles(const RtTriScene& t, int inst, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    // the relinked pair records: only with every instance staged (the root's meta rides in its record), as in the frame kernels
+    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= rtk::kWideBlas;
+    if (pairs && t.p16_ok) rtk::launch_qt<uint16_t, true, true, true, true>(t, rays, hits, n, s);
+    else if (pairs)        rtk::launch_qt<uint16_t, true, true, false, true>(t, rays, hits, n, s);
+    else if (inst)         rtk::launch_qt_walk<true>(t, rays, hits, n, s);
+    else                   rtk::launch_qt_walk<false>(t, rays, hits, n, s);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_query_spheres(const float* records, uint32_t n_spheres, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
+    hipLaunchKernelGGL(rtk::query_spheres, dim3(blocks), dim3(rtk::kQueryThreads), 0, s, records, n_spheres, rays, hits, n);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_pick_rays(const RtFrameArgs& a, const uint32_t* xy, float4* rays, uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(rtk::pick_rays, dim3((uint32_t)(((size_t)n + 255u) / 256u)), dim3(256), 0, s, a, xy, rays, n);
+    return hipGetLastError();
+}

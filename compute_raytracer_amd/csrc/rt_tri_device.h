@@ -51,7 +51,9 @@ __device__ __forceinline__ NodeR load_node_head(const RtTriScene& T, const TriLd
     n.hi = V(b.x, b.y, b.z); n.count = b.w;
     return n;
 }
-template <int WAVES, uint32_t NODES = kLdsNodes, uint32_t BLAS = kLdsBlas, bool INST = false>
+// ROOTS = false: the caller never passes pair records with this form (ray queries without the instance data in their arguments) --
+// no dynamically indexed read of T.root_meta, which would copy the whole argument block to scratch.
+template <int WAVES, uint32_t NODES = kLdsNodes, uint32_t BLAS = kLdsBlas, bool INST = false, bool ROOTS = true>
 __device__ __forceinline__ TriLds stage_head(const RtTriScene& T, float4* s_nodes, float* s_blas) {
     TriLds L;
     L.n_nodes = T.n_nodes < NODES ? T.n_nodes : NODES;
@@ -76,7 +78,7 @@ __device__ __forceinline__ TriLds stage_head(const RtTriScene& T, float4* s_node
     // node itself is then never loaded)
     for (uint32_t i = threadIdx.x; i < 20u * L.n_blas; i += 64 * WAVES) {
         float v = (i % 20u == 19u && i / 20u < L.n_lookup) ? T.blas_lookup[i / 20u] : T.blas[i];
-        if (T.pairs && i % 20u == 17u) v = __uint_as_float(T.root_meta[i / 20u]);
+        if (ROOTS && T.pairs && i % 20u == 17u) v = __uint_as_float(T.root_meta[i / 20u]);
         s_blas[i] = v;
     }
     __syncthreads();

@@ -57,3 +57,8 @@ hipError_t rt_launch_order_hist(uint32_t* cost, uint32_t* scan, uint32_t* order,
                                 hipStream_t s);   // (+ the frame's epilogue); split_out: pinned word that receives the number of tiles the list splits, or null
 hipError_t rt_launch_order_scatter(uint32_t* cost, uint32_t* scan, uint32_t* order, uint32_t n_tiles, hipStream_t s);
 hipError_t rt_launch_tri_corners(float4* out, const float* tri, const float* lookup, uint32_t n_slots, uint32_t n_tri, hipStream_t s);
+// Ray queries (rt_query.hip; include/rt355.h: rt_trace_rays): rays [n][2] float4 {origin, -}, {dir, -}, hits [n][2] float4 (rt_hit).
+// inst: the instance data travels in t.inst (stage_head<..., true>), as for the small forms; t.pairs only with inst.
+hipError_t rt_launch_query_triangles(const RtTriScene& t, int inst, const float4* rays, float4* hits, uint32_t n, hipStream_t s);
+hipError_t rt_launch_query_spheres(const float* records, uint32_t n_spheres, const float4* rays, float4* hits, uint32_t n, hipStream_t s);
+hipError_t rt_launch_pick_rays(const RtFrameArgs& a, const uint32_t* xy, float4* rays, uint32_t n, hipStream_t s);   // xy: [n][2] u32

@@ -153,6 +153,78 @@ class RendererRaytracing:
     def read_pixels_wait(self):
         abi.check(self._lib.rt_read_pixels_wait(self._ctx), self._ctx)
 
+    # ---- ray queries: the nearest hit of the host's rays (rt_trace_rays / rt_trace_rays_host / rt_pick) ----------------------
+    def trace_rays(self, origins, directions=None, out=None):
+        """Nearest hit of each ray against the scene the next frame would render (recalculateScene() first, as render() does).
+
+        numpy: origins and directions (n, 3) -> dict of numpy arrays t, u, v, prim, instance (n,) and normal (n, 3), through
+        rt_trace_rays_host.  torch: `origins` is a float32 (n, 8) tensor {origin, -, dir, -} on this renderer's device and
+        `directions` is None -> an (n, 8) float32 tensor of rt_hit records (prim / instance as int32 bits: .view(torch.int32)),
+        or `out`, enqueued through rt_trace_rays on torch.cuda.current_stream()."""
+        if type(origins).__module__.split(".")[0] == "torch":
+            return self._trace_rays_torch(origins, directions, out)
+        o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
+        if o.shape != d.shape:
+            raise ValueError("trace_rays: origins and directions must both be (n, 3)")
+        rays = np.zeros((o.shape[0], 8), dtype=np.float32)
+        rays[:, 0:3] = o
+        rays[:, 4:7] = d
+        self.recalculateScene()
+        hits = np.zeros(o.shape[0], dtype=abi.HIT_DTYPE)
+        abi.check(self._lib.rt_trace_rays_host(self._ctx, rays.ctypes.data, rays.shape[0], hits.ctypes.data), self._ctx)
+        return self._hit_dict(hits)
+
+    def _trace_rays_torch(self, rays, directions, out):
+        import torch
+        if directions is not None:
+            raise ValueError("trace_rays: a tensor argument is the (n, 8) ray buffer itself")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("trace_rays: rays must be a contiguous float32 (n, 8) tensor")
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise ValueError("trace_rays: rays must live on cuda:%d, this renderer's device" % self.device)
+        if out is None:
+            out = torch.empty((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
+        elif out.element_size() != 4 or tuple(out.shape) != (rays.shape[0], 8) or not out.is_contiguous() or out.device != rays.device:
+            raise ValueError("trace_rays: out must be a contiguous 32-bit (n, 8) tensor on the rays' device")
+        self.recalculateScene()
+        cur = torch.cuda.current_stream(rays.device)
+        # (torch's default stream has the handle 0, which the C ABI reads as "the context's stream": go through a stream of our own
+        # ordered after and before it)
+        run = cur
+        if cur.cuda_stream == 0:
+            if getattr(self, "_query_stream", None) is None:
+                self._query_stream = torch.cuda.Stream(rays.device)
+            run = self._query_stream
+            run.wait_stream(cur)
+        abi.check(self._lib.rt_trace_rays(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0],
+                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(run.cuda_stream)), self._ctx)
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
+    def pick(self, x, y):
+        """What pixel (x, y) of the next frame sees first: its primary ray's nearest hit (full-frame coordinates, scalars or arrays
+        that broadcast).  Triangle scenes add `mesh`, the instance's mesh index (-1 on a miss)."""
+        xs, ys = np.broadcast_arrays(np.asarray(x, dtype=np.int64), np.asarray(y, dtype=np.int64))
+        shape = xs.shape
+        xy = np.stack([xs.reshape(-1), ys.reshape(-1)], axis=1)
+        xy = np.ascontiguousarray(np.where(xy < 0, 0xFFFFFFFF, xy).astype(np.uint32))   # negatives: outside the frame
+        self.recalculateScene()
+        hits = np.zeros(xy.shape[0], dtype=abi.HIT_DTYPE)
+        abi.check(self._lib.rt_pick(self._ctx, xy.ctypes.data, xy.shape[0], hits.ctypes.data), self._ctx)
+        res = self._hit_dict(hits)
+        if self.scene.hasTriangles:
+            mesh_index = np.asarray(self.scene.instances.mesh_index, dtype=np.int64)
+            inst = res["instance"]
+            res["mesh"] = np.where(inst >= 0, mesh_index[np.clip(inst, 0, len(mesh_index) - 1)], -1)
+        return {k: v.reshape(shape + v.shape[1:]) for k, v in res.items()}
+
+    @staticmethod
+    def _hit_dict(hits):
+        return {"t": hits["t"].copy(), "u": hits["u"].copy(), "v": hits["v"].copy(), "prim": hits["prim"].copy(),
+                "instance": hits["instance"].copy(), "normal": np.ascontiguousarray(hits["normal"])}
+
     def stats(self):
         st = abi.RtStats()
         abi.check(self._lib.rt_get_stats(self._ctx, ctypes.byref(st)), self._ctx)

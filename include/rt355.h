@@ -262,6 +262,40 @@ int rt_assemble_frame(rt_ctx* ctx, const void* gathered, void* frame, uint32_t w
  * rt_render / rt_resize / rt_destroy). */
 int rt_device_pixels(rt_ctx* ctx, void** out_ptr, size_t* out_bytes);
 
+/* ---- ray queries: the nearest hit of rays the host supplies (RK:168-244 / RK:311-322 without the shading) ------------------ */
+
+/* One ray: 8 f32 = {origin.xyz, reserved, dir.xyz, reserved}.  Reserved words are ignored (kept for a later per-ray limit).
+ * dir need not be unit length; t is in units of |dir|, as in the reference's arithmetic. */
+typedef struct rt_hit {
+    float t;          /* nearest hit, RK:168-244 traceTLAS / RK:311-322 over spheres: tMin 0.001, search starts at 9999; -1 on a miss */
+    float u, v;       /* triangle barycentrics of RK:378-379 (object space); 0 for spheres and misses                        */
+    int32_t prim;     /* triangle: u32(triangleLookup[slot]) (index into rt_write_triangles' records); sphere: record index; -1 miss */
+    int32_t instance; /* triangle: BLAS record index bi of RK:223 (= order of rt_write_blas = scene.instances); -1 spheres / miss */
+    float normal[3];  /* the renderer's shading normal: RK:334-338 (transpose(inverseModel) * n, normalised) / HK:320; 0 on a miss */
+} rt_hit;             /* 32 bytes */
+
+/* rt_trace_rays: `rays` ([n][8] f32) and `hits` ([n] rt_hit) in device memory of this context's GPU, 16-byte aligned; enqueued on
+ * `hip_stream` (NULL = the context's stream), returns at once, like rt_render_to.  rt_trace_rays_host: host memory, synchronous
+ * (staged through device buffers the context owns, which grow as needed).  rt_pick: the primary ray of each pixel (x, y) --
+ * xy = [n][2] u32 -- under the current rt_write_params and rt_resize, exactly the ray that pixel of the next frame starts with;
+ * host memory, synchronous.  Coordinates are full-frame even under rt_set_partition; one outside W x H: RT_ERR_INVALID_ARG.
+ *
+ * Contract.
+ *   - A query sees the scene the next rt_render would render: every rt_write_* made before it, on any stream, per-frame
+ *     instance writes that no frame has carried yet included.  Results are bit for bit the reference's arithmetic (the
+ *     oracle's rt_oracle_trace_tri_rays / hit_sphere); sphere scenes are searched with the literal loop, every sphere in
+ *     index order (the lowest index wins a tie).
+ *   - n == 0: RT_OK, nothing done.  A NULL pointer: RT_ERR_INVALID_ARG.  No scene written: RT_ERR_STATE.
+ *   - Queries are not frames: they take no slot of the event ring, change no field of rt_stats, have no rt_kernel_id, and are
+ *     unaffected by rt_select_kernel, rt_set_mode and rt_set_variant.
+ *   - Frames in flight are never disturbed.  A query waits for the last scene update, not for frames; it drains only where a
+ *     frame would: the first query or frame after rt_write_triangles / _tri_lookup builds the library's corner array, and a
+ *     scene whose instance data does not travel with frames (more than sixteen instances) may need its per-frame buffers
+ *     brought up to date.  Queries run in call order, whatever their streams; scene writes after a query wait for it. */
+int rt_trace_rays(rt_ctx* ctx, const float* rays, uint32_t n, rt_hit* hits, void* hip_stream);  /* device memory, async     */
+int rt_trace_rays_host(rt_ctx* ctx, const float* rays, uint32_t n, rt_hit* hits);               /* host memory, synchronous */
+int rt_pick(rt_ctx* ctx, const uint32_t* xy, uint32_t n, rt_hit* hits);                         /* host memory, synchronous */
+
 /* ---- multi-GPU: render + RCCL gather behind one call (RR:434-470 across a group of GPUs) ------ */
 
 /* One process per GPU.  Rank 0 calls rt_comm_unique_id and hands the bytes to the other ranks by

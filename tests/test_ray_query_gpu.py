@@ -1,0 +1,368 @@
+"""Ray queries on the MI355X (include/rt355.h: rt_trace_rays, rt_trace_rays_host, rt_pick) against the CPU oracle, bit for bit:
+triangle scenes against oracle.trace_tri_rays plus a float32 restatement of the hit (RK:344-381, RK:334-338), sphere scenes
+against rt_oracle_np._trace and oracle.hit_sphere; the pose a query sees after scene.update() without a frame; picking; queries
+beside frames in flight; the three paths against each other."""
+
+import numpy as np
+import pytest
+
+import compute_raytracer_amd as rt
+from compute_raytracer_amd import abi
+from helpers import deepen_top_level, leafy_scene, ref_fixture, spine_scene, tri_buffers, triangle_scene
+from oracle import rt_oracle_np
+
+pytestmark = pytest.mark.gpu
+F = np.float32
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def same(a, b):
+    return np.array_equal(bits(a), bits(b))
+
+
+def make_renderer(scene, mat=None, W=96, H=64, sky=None):
+    r = rt.RendererRaytracing(W, H, scene, maxBounces=2).initialize(sky, mat)
+    r.recalculateScene()
+    return r
+
+
+# ---- rays --------------------------------------------------------------------------------------------------------------------
+def camera_rays(scene, W, H, step=1):
+    """The primary rays of a W x H frame (RK:76-86 in float32, the oracle's order), every `step`-th pixel."""
+    p = scene.pack_params(2)
+    cam, fw, rgt, up = p[0:3], p[4:7], p[8:11], p[12:15]
+    ys, xs = np.mgrid[0:H:step, 0:W:step]
+    xs = xs.reshape(-1); ys = ys.reshape(-1)
+    hc = (xs.astype(F) - F(W) / F(2)) / F(W) * F(2)
+    vc = (F(H) / F(2) - ys.astype(F)) / F(W) * F(2)
+    d = np.stack([(fw[k] + hc * rgt[k]) + vc * up[k] for k in range(3)], axis=1).astype(F)
+    ln = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+    d = d / ln[:, None]
+    return np.broadcast_to(cam, d.shape).astype(F), d.astype(F)
+
+
+def random_rays(lo, hi, n, seed):
+    """Incoherent rays: origins in the box grown by half its size on every side (inside and outside the scene), directions of
+    lengths 0.05 .. 20 (not unit)."""
+    rng = np.random.default_rng(seed)
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    ext = hi - lo
+    o = rng.uniform(lo - 0.5 * ext, hi + 0.5 * ext, (n, 3)).astype(F)
+    d = rng.normal(size=(n, 3))
+    d = d / np.linalg.norm(d, axis=1)[:, None] * rng.uniform(0.05, 20.0, (n, 1))
+    return o, d.astype(F)
+
+
+def axis_rays(lo, hi, seed, per_axis=100):
+    """Directions along the axes (the inverse direction is +-inf in two components)."""
+    rng = np.random.default_rng(seed)
+    o = rng.uniform(lo, hi, (6 * per_axis, 3)).astype(F)
+    d = np.zeros((6 * per_axis, 3), F)
+    for k in range(6):
+        d[k * per_axis:(k + 1) * per_axis, k // 2] = F(1.0 if k % 2 == 0 else -1.0) * F(0.5 + k)
+    return o, d
+
+
+def scene_box(buf, scene):
+    """The top-level root's box, within 20 of the camera (the reference's floor spans millions)."""
+    root, cam = buf["nodes"][0], scene.pack_params(2)[0:3]
+    return np.maximum(root[0:3], cam - 20.0), np.minimum(root[4:7], cam + 20.0)
+
+
+# ---- the triangle hit restated in float32 --------------------------------------------------------------------------------------
+def dot(a, b):
+    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
+
+
+def cross(a, b):
+    return np.stack([a[..., 1] * b[..., 2] - b[..., 1] * a[..., 2], a[..., 2] * b[..., 0] - b[..., 2] * a[..., 0],
+                     a[..., 0] * b[..., 1] - b[..., 0] * a[..., 1]], axis=-1)
+
+
+def mat_apply(m, v, w):
+    """mat4 (column-major, m[4c + r]) * vec4(v, w), summed over columns left to right (RK:254-255)."""
+    return np.stack([((m[:, r] * v[:, 0] + m[:, 4 + r] * v[:, 1]) + m[:, 8 + r] * v[:, 2]) + m[:, 12 + r] * F(w) for r in range(3)], axis=1)
+
+
+def restate_triangle_hits(buf, o, d, prim, inst):
+    """t, u, v (RK:354-379) of triangle `prim` in the object space of instance `inst`, and the shading normal (RK:381-382,
+    RK:334-338): every operation a float32 operation, in the oracle's order."""
+    m = np.asarray(buf["blas"], F).reshape(-1, 20)[inst]
+    tri = np.asarray(buf["triangles"], F).reshape(-1, 40)[prim]
+    oo, od = mat_apply(m, o, 1.0), mat_apply(m, d, 0.0)
+    A, B, C = tri[:, 0:3], tri[:, 12:15], tri[:, 24:27]
+    e1, e2 = B - A, C - A
+    rce2 = cross(od, e2)
+    det = dot(e1, rce2)
+    s = oo - A
+    u = dot(s, rce2)
+    sce1 = cross(s, e1)
+    v = dot(od, sce1)
+    inv = F(1.0) / det
+    t = inv * dot(e2, sce1)
+    u = u * inv
+    v = v * inv
+    w = (F(1.0) - u) - v
+    n = (w[:, None] * tri[:, 4:7] + u[:, None] * tri[:, 16:19]) + v[:, None] * tri[:, 28:31]
+    tn = np.stack([((m[:, 4 * r + 0] * n[:, 0] + m[:, 4 * r + 1] * n[:, 1]) + m[:, 4 * r + 2] * n[:, 2]) + m[:, 4 * r + 3] * F(0.0)
+                   for r in range(3)], axis=1)
+    nrm = tn / np.sqrt(dot(tn, tn))[:, None]
+    return t, u, v, nrm
+
+
+def check_triangle_hits(oracle, buf, o, d, h):
+    t_ref = oracle.trace_tri_rays(buf, o, d)
+    miss = h["prim"] < 0
+    assert np.array_equal(miss, t_ref == F(-1.0)), "miss sets differ: %d vs %d" % (miss.sum(), (t_ref == -1).sum())
+    assert same(h["t"], t_ref), "t differs from the oracle on %d rays" % int((bits(h["t"]) != bits(t_ref)).sum())
+    assert np.all(h["instance"][miss] == -1) and np.all(h["u"][miss] == 0) and np.all(h["v"][miss] == 0)
+    assert np.all(h["normal"][miss] == 0)
+    hit = ~miss
+    if hit.any():
+        assert np.all(h["instance"][hit] >= 0) and np.all(h["prim"][hit] < len(buf["triangles"]))
+        with np.errstate(all="ignore"):
+            t, u, v, nrm = restate_triangle_hits(buf, o[hit], d[hit], h["prim"][hit], h["instance"][hit])
+        assert same(t, h["t"][hit]) and same(u, h["u"][hit]) and same(v, h["v"][hit])
+        assert same(nrm, h["normal"][hit])
+    return int(hit.sum())
+
+
+def tri_cases():
+    def insts(k):                     # triangle_scene adds a floor to its k models
+        return lambda: triangle_scene(seed=40 + k, n_models=k - 1)
+    def deep():
+        scene, mat = triangle_scene(seed=50, n_models=3)
+        deepen_top_level(scene, 3)
+        return scene, mat
+    return {
+        "ref": lambda: (ref_fixture()[0], rt.Material.white()),
+        "spine24": lambda: (spine_scene(24), rt.Material.white()),
+        "leafy3": lambda: (leafy_scene(3), rt.Material.white()),
+        "deepened": deep,
+        "inst1": insts(1), "inst3": insts(3), "inst5": insts(5), "inst13": insts(13), "inst17": insts(17),
+    }
+
+
+CASES = tri_cases()
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_triangles_against_the_oracle(oracle, name):
+    scene, mat = CASES[name]()
+    W, H = (336, 212) if name == "ref" else (160, 100)
+    r = make_renderer(scene, mat, W, H)
+    try:
+        buf = tri_buffers(scene, mat)
+        lo, hi = scene_box(buf, scene)
+        sets = [camera_rays(scene, W, H), random_rays(lo, hi, 10000, 7), axis_rays(lo, hi, 8)]
+        hits = 0
+        for o, d in sets:
+            h = r.trace_rays(o, d)
+            hits += check_triangle_hits(oracle, buf, o, d, h)
+        assert hits > 100                 # the rays do meet the scene
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("n_inst", [3, 17])
+def test_query_sees_the_pose_no_frame_has_carried(oracle, n_inst):
+    """scene.update() and then a query without a frame: the result is the NEW pose's (the small frame forms carry their instance
+    data in their arguments; the device's per-frame buffers lag behind)."""
+    scene, mat = triangle_scene(seed=60 + n_inst, n_models=n_inst - 1)
+    W, H = 160, 100
+    r = make_renderer(scene, mat, W, H)
+    try:
+        r.render()                                        # a frame carries the first pose
+        old = tri_buffers(scene, mat)
+        scene.update(0.5)
+        new = tri_buffers(scene, mat)
+        o, d = camera_rays(scene, W, H)
+        h = r.trace_rays(o, d)
+        check_triangle_hits(oracle, new, o, d, h)
+        assert not same(oracle.trace_tri_rays(old, o, d), h["t"])     # the poses differ where the rays look
+        scene.update(0.5)                                 # and a pick, again without a frame
+        ys, xs = np.mgrid[0:H:7, 0:W:7]
+        p = r.pick(xs.reshape(-1), ys.reshape(-1))
+        params = scene.pack_params(2)
+        dirs = np.stack([oracle.ray_dir(params, W, H, int(x), int(y)) for x, y in zip(xs.reshape(-1), ys.reshape(-1))])
+        orig = np.broadcast_to(params[0:3], dirs.shape).astype(F)
+        check_triangle_hits(oracle, tri_buffers(scene, mat), orig, dirs, p)
+    finally:
+        r.close()
+
+
+def sphere_scene_with_duplicates():
+    scene = rt.synthetic_scene(24, 5)
+    scene.spheres = list(scene.spheres) + list(scene.spheres)      # equal t for every pair: the lower index wins
+    return scene
+
+
+@pytest.mark.parametrize("n", [1, 37, 1024, 5000, "dup"])
+def test_spheres_against_the_oracle(oracle, n):
+    scene = sphere_scene_with_duplicates() if n == "dup" else rt.synthetic_scene(n, 11)
+    sp = np.asarray(scene.pack_spheres(), F).reshape(-1, 8)
+    r = make_renderer(scene)
+    try:
+        lo, hi = (sp[:, 0:3] - sp[:, 7:8]).min(axis=0), (sp[:, 0:3] + sp[:, 7:8]).max(axis=0)
+        count = 2048 if sp.shape[0] > 1000 else 10000
+        for o, d in [camera_rays(scene, 96, 64), random_rays(lo, hi, count, 3), axis_rays(lo, hi, 4, 50)]:
+            h = r.trace_rays(o, d)
+            with np.errstate(all="ignore"):
+                nearest, idx = rt_oracle_np._trace(sp, o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2])
+            miss = idx < 0
+            assert np.array_equal(h["prim"], np.where(miss, -1, idx).astype(np.int32))
+            assert same(h["t"], np.where(miss, F(-1.0), nearest))
+            assert np.all(h["instance"] == -1) and np.all(h["u"] == 0) and np.all(h["v"] == 0) and np.all(h["normal"][miss] == 0)
+            hit = np.nonzero(~miss)[0]
+            assert hit.size > 0
+            if n == "dup":
+                assert np.all(h["prim"][hit] < sp.shape[0] // 2)
+            for i in hit[:: max(1, hit.size // 200)]:
+                ok, t, nrm = oracle.hit_sphere(o[i], d[i], sp[h["prim"][i]], 0.001, 9999.0)
+                assert ok and same(t, h["t"][i]) and same(nrm, h["normal"][i])
+    finally:
+        r.close()
+
+
+def test_pick_against_the_oracle(oracle):
+    scene, mat = triangle_scene(seed=70, n_models=4)
+    W, H = 203, 118                                       # a ragged last tile row and column
+    r = make_renderer(scene, mat, W, H)
+    try:
+        xs = np.r_[np.arange(0, W, 13), W - 1]
+        ys = np.r_[np.arange(0, H, 9), H - 1]
+        gx, gy = np.meshgrid(xs, ys)
+        params = scene.pack_params(2)
+        dirs = np.stack([oracle.ray_dir(params, W, H, int(x), int(y)) for x, y in zip(gx.reshape(-1), gy.reshape(-1))])
+        orig = np.broadcast_to(params[0:3], dirs.shape).astype(F)
+        buf = tri_buffers(scene, mat)
+        p = r.pick(gx, gy)
+        assert p["t"].shape == gx.shape and p["normal"].shape == gx.shape + (3,)
+        flat = {k: v.reshape((-1,) + v.shape[gx.ndim:]) for k, v in p.items()}
+        assert check_triangle_hits(oracle, buf, orig, dirs, flat) > 10
+        mesh = np.asarray(scene.instances.mesh_index)
+        assert np.array_equal(flat["mesh"], np.where(flat["instance"] >= 0, mesh[np.maximum(flat["instance"], 0)], -1))
+        one = r.pick(int(gx[3, 4]), int(gy[3, 4]))
+        assert one["t"].shape == () and same(one["t"], p["t"][3, 4])
+        for x, y in [(W, 0), (0, H), (-1, 0)]:
+            with pytest.raises(abi.RtError) as e:
+                r.pick(x, y)
+            assert e.value.code == abi.RT_ERR_INVALID_ARG
+        # under a partition, coordinates stay full-frame (rows of tiles this rank does not render included)
+        abi.check(r._lib.rt_set_partition(r._ctx, 1, 2), r._ctx)
+        q = r.pick(gx, gy)
+        for k in p:
+            assert np.array_equal(np.ascontiguousarray(q[k]).view(np.uint8), np.ascontiguousarray(p[k]).view(np.uint8)), k
+    finally:
+        r.close()
+
+
+def test_queries_do_not_disturb_frames(oracle):
+    import torch
+    scene, mat = triangle_scene(seed=80, n_models=3)
+    W, H = 200, 120
+    r = make_renderer(scene, mat, W, H)
+    try:
+        sky = r.skyboxMaterial
+        ref, _, ref_rays = oracle.render_tri(scene.pack_params(2), tri_buffers(scene, mat), sky.faces, W, H)
+        r.render()
+        buf = tri_buffers(scene, mat)
+        o, d = camera_rays(scene, W, H, 3)
+        rays = np.zeros((o.shape[0], 8), F)
+        rays[:, 0:3], rays[:, 4:7] = o, d
+        dev = torch.from_numpy(rays).to("cuda:0")
+        frames = r.host_frames(4)
+
+        def batch(query):
+            for _ in range(4):
+                r.enqueue()
+            out = None
+            if query:
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    out = r.trace_rays(dev)
+            r.enqueue()
+            for k in range(4):
+                r.read_pixels_async(k, frames[k])
+            r.wait()
+            r.read_pixels_wait()
+            if query:
+                side.synchronize()
+            return out
+
+        batch(False)
+        batch(False)                      # (the library now knows the caller keeps frames in flight: the same form for both)
+        s0 = r.stats()
+        out = batch(True)
+        s1 = r.stats()
+        for f in frames + [r.read_pixels()]:
+            assert np.array_equal(f, ref)
+        assert s1["frames"] == s0["frames"] + 5 and s1["batch_frames"] == s0["batch_frames"]
+        for k in ("rays", "kernel_id", "tri_form"):
+            assert s1[k] == s0[k], k
+        assert s1["rays"] == ref_rays
+        before = r.stats()
+        h = out.cpu().numpy()
+        hd = r.trace_rays(o, d)
+        assert r.stats() == before                               # a query changes no statistic
+        check_triangle_hits(oracle, buf, o, d, hd)
+        host = np.zeros(o.shape[0], dtype=abi.HIT_DTYPE)
+        abi.check(r._lib.rt_trace_rays_host(r._ctx, rays.ctypes.data, rays.shape[0], host.ctypes.data), r._ctx)
+        want = h.view(np.uint32)
+        assert np.array_equal(want.reshape(-1), host.view(np.uint32))
+        # heatmap, strict mode, the node-walk variant: the same answers
+        for setup in (r.showHeatmap, lambda: (r.showRaytracer(), r.set_mode(True)), lambda: r.set_variant(6)):
+            setup()
+            again = r.trace_rays(dev).cpu().numpy().view(np.uint32)
+            assert np.array_equal(again, want)
+    finally:
+        r.close()
+
+
+def test_device_host_and_pick_paths_agree():
+    import torch
+    scene, mat = triangle_scene(seed=90, n_models=5)
+    W, H = 150, 90
+    r = make_renderer(scene, mat, W, H)
+    lib = r._lib
+    try:
+        ys, xs = np.mgrid[0:H:4, 0:W:4]
+        p = r.pick(xs.reshape(-1), ys.reshape(-1))
+        hits = np.zeros(p["t"].shape[0], dtype=abi.HIT_DTYPE)
+        xy = np.ascontiguousarray(np.stack([xs.reshape(-1), ys.reshape(-1)], 1).astype(np.uint32))
+        abi.check(lib.rt_pick(r._ctx, xy.ctypes.data, xy.shape[0], hits.ctypes.data), r._ctx)
+        o, d = camera_rays(scene, W, H, 4)
+        rays = np.zeros((o.shape[0], 8), F)
+        rays[:, 0:3], rays[:, 4:7] = o, d
+        host = np.zeros_like(hits)
+        abi.check(lib.rt_trace_rays_host(r._ctx, rays.ctypes.data, rays.shape[0], host.ctypes.data), r._ctx)
+        dev = r.trace_rays(torch.from_numpy(rays).to("cuda:0"))
+        torch.cuda.synchronize()
+        assert np.array_equal(hits.view(np.uint8), host.view(np.uint8))
+        assert np.array_equal(dev.cpu().numpy().view(np.uint8).reshape(-1), host.view(np.uint8))
+        out = torch.full((rays.shape[0], 8), 7.0, device="cuda:0")
+        assert r.trace_rays(torch.from_numpy(rays).to("cuda:0"), out=out) is out
+        torch.cuda.synchronize()
+        assert np.array_equal(out.cpu().numpy().view(np.uint8).reshape(-1), host.view(np.uint8))
+        # n == 0: nothing to do
+        assert lib.rt_trace_rays_host(r._ctx, None, 0, None) == abi.RT_OK
+        assert lib.rt_trace_rays(r._ctx, None, 0, None, None) == abi.RT_OK
+        assert lib.rt_pick(r._ctx, None, 0, None) == abi.RT_OK
+        assert lib.rt_trace_rays_host(r._ctx, None, 4, None) == abi.RT_ERR_INVALID_ARG
+    finally:
+        r.close()
+    # a context without a scene
+    bare = rt.RendererRaytracing(16, 16, rt.synthetic_scene(3, 1)).initialize()
+    try:
+        rays = np.zeros((1, 8), F)
+        rays[0, 6] = -1.0
+        hits = np.zeros(1, dtype=abi.HIT_DTYPE)
+        assert bare._lib.rt_trace_rays_host(bare._ctx, rays.ctypes.data, 1, hits.ctypes.data) == abi.RT_ERR_STATE
+        xy = np.zeros((1, 2), np.uint32)
+        assert bare._lib.rt_pick(bare._ctx, xy.ctypes.data, 1, hits.ctypes.data) == abi.RT_ERR_STATE
+    finally:
+        bare.close()

@@ -1,0 +1,94 @@
+"""Dev tool: the rate of ray queries (rt_trace_rays) beside the per-ray cost of an awaited frame of the reference's scene.
+
+    rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o q -- python tools/query_rate.py
+
+Workloads: the 1344x846 primary rays of the reference's scene (tests/golden/ref_scene.npz), 2^20 random rays on it (origins in
+the scene box, within 20 of the camera, grown by half, directions of random length), 2^20 random rays on C3 (1024 spheres).  Each
+runs REPS times through the device path on one stream; the kernel statistics of rocprofv3 (query_triangles / query_spheres) give
+the rays per ms of the query kernels, and the line printed here gives the same from hipEvents around the batch.  The frame's
+figure is rt_stats.rays / kernel_ms of an awaited frame (RK:114 + RK:153 traversals, reflections and shadow rays included)."""
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import compute_raytracer_amd as rt  # noqa: E402
+
+REPS = 20
+
+
+def ray_tensor(torch, o, d):
+    rays = np.zeros((o.shape[0], 8), np.float32)
+    rays[:, 0:3], rays[:, 4:7] = o, d
+    return torch.from_numpy(rays).to("cuda:0")
+
+
+def camera(scene, W, H):
+    p = scene.pack_params(4)
+    F = np.float32
+    ys, xs = np.mgrid[0:H, 0:W]
+    hc = (xs.reshape(-1).astype(F) - F(W) / F(2)) / F(W) * F(2)
+    vc = (F(H) / F(2) - ys.reshape(-1).astype(F)) / F(W) * F(2)
+    d = np.stack([(p[4 + k] + hc * p[8 + k]) + vc * p[12 + k] for k in range(3)], axis=1)
+    d = d / np.linalg.norm(d, axis=1)[:, None]
+    return np.broadcast_to(p[0:3], d.shape).astype(F), d.astype(F)
+
+
+def random_rays(lo, hi, n, seed):
+    rng = np.random.default_rng(seed)
+    ext = hi - lo
+    o = rng.uniform(lo - 0.5 * ext, hi + 0.5 * ext, (n, 3)).astype(np.float32)
+    d = rng.normal(size=(n, 3))
+    d = d / np.linalg.norm(d, axis=1)[:, None] * rng.uniform(0.05, 20.0, (n, 1))
+    return o, d.astype(np.float32)
+
+
+def timed(torch, r, rays):
+    out = torch.empty_like(rays)
+    r.trace_rays(rays, out=out)                   # warm-up (first-use work: corner array, code objects)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(REPS):
+        r.trace_rays(rays, out=out)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / REPS
+    hits = int((out[:, 3].view(torch.int32) >= 0).sum().item())
+    return {"rays": int(rays.shape[0]), "ms": round(ms, 4), "rays_per_ms": round(rays.shape[0] / ms), "hit_fraction": round(hits / rays.shape[0], 3)}
+
+
+def main():
+    import torch
+    d = np.load(os.path.join(ROOT, "tests", "golden", "ref_scene.npz"))
+    scene = rt.SceneRaytracing.from_packed(d)
+    W, H = int(d["W"]), int(d["H"])
+    r = rt.RendererRaytracing(W, H, scene, maxBounces=int(d["maxBounces"])).initialize(None, rt.Material.white())
+    out = {}
+    for _ in range(5):
+        r.render()
+    st = r.stats()
+    out["ref_frame"] = {"rays": st["rays"], "kernel_ms": round(st["kernel_ms"], 4), "rays_per_ms": round(st["rays"] / st["kernel_ms"])}
+    out["ref_primary"] = timed(torch, r, ray_tensor(torch, *camera(scene, W, H)))
+    root = np.asarray(scene.pack_tlas_nodes(), np.float64).reshape(-1, 8)[0]
+    cam = scene.pack_params(4)[0:3].astype(np.float64)                  # (the floor's box spans millions: within 20 of the camera)
+    lo, hi = np.maximum(root[0:3], cam - 20.0), np.minimum(root[4:7], cam + 20.0)
+    out["ref_random_2^20"] = timed(torch, r, ray_tensor(torch, *random_rays(lo, hi, 1 << 20, 1)))
+    r.close()
+    cfg = rt.BASELINE_CONFIGS["C3"]
+    c3 = rt.synthetic_scene(cfg["spheres"], cfg["seed"])
+    r = rt.RendererRaytracing(256, 256, c3, maxBounces=cfg["bounces"]).initialize()
+    r.recalculateScene()
+    sp = np.asarray(c3.pack_spheres(), np.float32).reshape(-1, 8)
+    lo, hi = (sp[:, 0:3] - sp[:, 7:8]).min(axis=0), (sp[:, 0:3] + sp[:, 7:8]).max(axis=0)
+    out["c3_random_2^20"] = timed(torch, r, ray_tensor(torch, *random_rays(lo.astype(np.float64), hi.astype(np.float64), 1 << 20, 2)))
+    r.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
