@@ -802,6 +802,18 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     const bool need_prep = !tri && c->n && (!c->prep_spheres_valid || (!use_bvh && !c->prep_params_valid));
     const bool need_bvh = use_bvh && !c->bvh_valid;
 
+    RtLaunchCfg cfg;
+    cfg.mode = filter_ok ? c->mode : (int)RT_MODE_STRICT;
+    cfg.variant = (c->variant == 4 || c->variant == 5) ? 0 : c->variant;   // rt_kernels.hip numbers its default 0
+    // A brute-force variant none of whose forms holds the scene (1 above 2,176 spheres, 2 and 3 above 3,264, up to the
+    // 4,608 from which every variant reads the records from global memory) is refused here: before anything of the frame
+    // is enqueued, a slot of the event ring is taken or the stats change.
+    if (!tri && !use_bvh && !rt_trace_fits(c->n, c->n16, cfg, queue_pipeline)) {
+        char buf[200];
+        std::snprintf(buf, sizeof buf, "rt_render: kernel variant %d has no form for %u spheres (its sphere records exceed the "
+                      "160 KiB of LDS); variant 0 renders any count", c->variant, c->n);
+        return fail(RT_ERR_UNSUPPORTED, buf);
+    }
     if (queue_pipeline) { int rc = ensure_queue(c); if (rc != RT_OK) return rc; }
     bool sky_flat = true;       // six 1x1 faces of one colour
     for (int i = 0; i < 6; ++i)
@@ -981,10 +993,6 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     fa.queue = queue_pipeline ? c->d_queue : nullptr;   // rt_kernels.hip takes the pipeline only with a queue
     fa.qctrl = reinterpret_cast<uint32_t*>(ctrl) + 2;
     fa.queue_cap = queue_pipeline ? (uint32_t)c->queue_cap : 0u;
-    RtLaunchCfg cfg;
-    cfg.mode = filter_ok ? c->mode : (int)RT_MODE_STRICT;
-    cfg.variant = (c->variant == 4 || c->variant == 5) ? 0 : c->variant;   // rt_kernels.hip numbers its default 0
-
     const uint32_t v = slot % (uint32_t)kVersions;
     RtTriScene ts;
     std::memset(&ts, 0, sizeof ts);

@@ -30,6 +30,8 @@
 //   * two-kernel pipeline: bounce 0 per pixel (coherent, cheap hoisted forms), then persistent
 //     waves that refill idle lanes from a path queue, so the expensive per-lane-origin trace
 //     runs with full waves.
+#include <cstring>
+
 #include "rt_filter.h"
 
 namespace rtk {
@@ -700,53 +702,63 @@ hipError_t launch_strict(const RtFrameArgs& a, hipStream_t s) {
     return launch_pixels<4, false, false, false, false, 1, true>(a, s);      // any N: records from global memory
 }
 
-template <bool SGN>
-hipError_t launch_fast(const RtFrameArgs& a, int variant, hipStream_t s) {
+// The brute-force forms of RT_MODE_FAST, as launch_fast picks them: from the sphere count, the variant and whether the frame
+// has a path queue.  FastNone: no form of the variant holds the scene -- the host refuses such a frame before it enqueues
+// anything of it (rt_trace_fits).
+enum FastForm { FastNone, FastGlobal, FastSingle, FastPipe8, FastPipe16, FastPipe8Global, FastV2, FastV3 };
+
+FastForm fast_form(const RtFrameArgs& a, int variant, bool queue) {
     const size_t rec = (size_t)a.N16 * 16u;
-    if (2 * rec + 8u * 8u * 256u > kLdsCap)                                  // > 4608 spheres: no LDS staging
-        return launch_pixels<4, true, false, SGN, false, 16, true>(a, s);
-    const bool small = 3 * rec + 3 * (rec / 4) + 8u * 16u * 256u <= 80u * 1024u;      // N <= ~800: 2 workgroups of 8 waves per CU
-    const bool pipeline = a.queue && a.qctrl && a.N >= 320u;   // measured crossover of the two brute-force forms
+    if (2 * rec + 8u * 8u * 256u > kLdsCap) return FastGlobal;                      // > 4608 spheres: no LDS staging
+    const bool pipeline = queue && a.N >= 320u;   // measured crossover of the two brute-force forms
     switch (variant) {
         case 0:   // default: two-kernel pipeline for scenes where the sphere loop dominates,
                   // single kernel for small scenes (the queue round trip costs more than it saves)
             if (pipeline) {
-                hipError_t e;
-                if (lds_paths<8, true, 16>(a) <= kLdsCap) {                      // N <= ~3600
-                    e = launch_first<8, SGN, true, 8>(a, s);
-                    if (e != hipSuccess) return e;
-                    return launch_paths<8, SGN, true, 16>(a, s);
-                }
+                if (lds_paths<8, true, 16>(a) <= kLdsCap) return FastPipe8;           // N <= 3264
                 // larger scenes: exact 4th components from global memory; 16-wave workgroups so
                 // that the one workgroup a CU can hold still gives 4 waves per SIMD
-                if (lds_paths<16, false, 8>(a) <= kLdsCap) {                     // N <= 4096
-                    e = launch_first<16, SGN, false, 4>(a, s);
-                    if (e != hipSuccess) return e;
-                    return launch_paths<16, SGN, false, 8>(a, s);
-                }
-                e = launch_first<8, SGN, false, 4>(a, s);                        // N <= 4608
-                if (e != hipSuccess) return e;
-                return launch_paths<8, SGN, false, 8>(a, s);
+                if (lds_paths<16, false, 8>(a) <= kLdsCap) return FastPipe16;         // N <= 4096
+                return FastPipe8Global;                                                // N <= 4608
             }
             [[fallthrough]];
-        case 1:   // single kernel
-            if (small) return launch_pixels<8, true, false, SGN, true, 16>(a, s);
-            if (lds_pixels<8, true, false, true, 16>(a) <= kLdsCap) return launch_pixels<8, true, false, SGN, true, 16>(a, s);
-            return hipErrorInvalidValue;   // > ~2700 spheres need the pipeline
+        case 1:   // single kernel (N <= ~800: 2 workgroups of 8 waves per CU)
+            if (lds_pixels<8, true, false, true, 16>(a) <= kLdsCap) return FastSingle;  // N <= 2176
+            return FastNone;   // larger scenes need the pipeline
         case 2:   // pipeline, 4-wave workgroups in the path stage
-            if (a.queue && a.qctrl && lds_paths<4, true, 16>(a) <= kLdsCap) {
-                hipError_t e = launch_pixels<8, true, true, SGN, true, 16>(a, s);
-                if (e != hipSuccess) return e;
-                return launch_paths<4, SGN, true, 16>(a, s);
-            }
-            return hipErrorInvalidValue;
+            if (queue && lds_pixels<8, true, true, true, 16>(a) <= kLdsCap && lds_paths<4, true, 16>(a) <= kLdsCap) return FastV2;  // N <= 3264
+            return FastNone;
         case 3:   // pipeline forced (also for small scenes)
-            if (a.queue && a.qctrl && lds_paths<8, true, 16>(a) <= kLdsCap) {
-                hipError_t e = launch_pixels<8, true, true, SGN, true, 16>(a, s);
-                if (e != hipSuccess) return e;
-                return launch_paths<8, SGN, true, 16>(a, s);
-            }
-            return hipErrorInvalidValue;
+            if (queue && lds_pixels<8, true, true, true, 16>(a) <= kLdsCap && lds_paths<8, true, 16>(a) <= kLdsCap) return FastV3;  // N <= 3264
+            return FastNone;
+        default:
+            return FastNone;
+    }
+}
+
+template <bool SGN>
+hipError_t launch_fast(const RtFrameArgs& a, int variant, hipStream_t s) {
+    hipError_t e;
+    switch (fast_form(a, variant, a.queue && a.qctrl)) {
+        case FastGlobal:
+            return launch_pixels<4, true, false, SGN, false, 16, true>(a, s);
+        case FastSingle:
+            return launch_pixels<8, true, false, SGN, true, 16>(a, s);
+        case FastPipe8:
+            e = launch_first<8, SGN, true, 8>(a, s);
+            return e != hipSuccess ? e : launch_paths<8, SGN, true, 16>(a, s);
+        case FastPipe16:
+            e = launch_first<16, SGN, false, 4>(a, s);
+            return e != hipSuccess ? e : launch_paths<16, SGN, false, 8>(a, s);
+        case FastPipe8Global:
+            e = launch_first<8, SGN, false, 4>(a, s);
+            return e != hipSuccess ? e : launch_paths<8, SGN, false, 8>(a, s);
+        case FastV2:
+            e = launch_pixels<8, true, true, SGN, true, 16>(a, s);
+            return e != hipSuccess ? e : launch_paths<4, SGN, true, 16>(a, s);
+        case FastV3:
+            e = launch_pixels<8, true, true, SGN, true, 16>(a, s);
+            return e != hipSuccess ? e : launch_paths<8, SGN, true, 16>(a, s);
         default:
             return hipErrorInvalidValue;
     }
@@ -758,6 +770,14 @@ hipError_t rt_launch_trace(const RtFrameArgs& a, const RtLaunchCfg& cfg, hipStre
     if (cfg.mode == 1) { g_rt_kernel_id = RT_KID_LITERAL; return rtk::launch_strict(a, s); }
     g_rt_kernel_id = RT_KID_BRUTE_SINGLE;          // launch_paths overrides it when the two-kernel pipeline runs
     return a.signed_filter ? rtk::launch_fast<true>(a, cfg.variant, s) : rtk::launch_fast<false>(a, cfg.variant, s);
+}
+
+bool rt_trace_fits(uint32_t n, uint32_t n16, const RtLaunchCfg& cfg, bool queue) {
+    if (cfg.mode == 1) return true;                // launch_strict: any N
+    RtFrameArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.N = n; a.N16 = n16;
+    return rtk::fast_form(a, cfg.variant, queue) != rtk::FastNone;
 }
 
 hipError_t rt_launch_prep(const RtPrepArgs& a, hipStream_t s) {

@@ -189,7 +189,9 @@ int rt_set_mode(rt_ctx* ctx, int mode);
  * 0 = bounding-sphere hierarchy from 128 spheres on (from 72 on once the caller keeps frames in flight), single
  * brute-force kernel below;
  * 4 = hierarchy for any sphere count; 5 = brute force (two-kernel pipeline from 320 spheres on);
- * 1, 2, 3 = individual brute-force forms.  Triangle scenes: 0 = one workgroup per tile (rt_triangles.hip), reading the BLAS
+ * 1, 2, 3 = individual brute-force forms; a frame none of whose forms holds the scene (variant 1 above 2,176 spheres, 2 and 3
+ * above 3,264, up to 4,608 -- beyond that each reads the records from global memory) fails rt_render with RT_ERR_UNSUPPORTED
+ * before anything of it is enqueued.  Triangle scenes: 0 = one workgroup per tile (rt_triangles.hip), reading the BLAS
  * trees from the library's relinked pair records where the scene fits them (up to 12 instances, node buffer and lookup table
  * within 16-bit indices); 6 = the same kernel on the reference's node buffer only.  Every variant produces the same pixels.
  * See DESIGN.md. */

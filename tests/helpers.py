@@ -2,7 +2,7 @@
 import numpy as np
 
 import compute_raytracer_amd as rt
-from compute_raytracer_amd.scene_raytracing import CONSTANT_SKY_RGBA
+from compute_raytracer_amd.scene_raytracing import CONSTANT_SKY_RGBA, synthetic_spheres
 
 
 def config_inputs(name, width=None, height=None, spheres=None, bounces=None):
@@ -323,3 +323,225 @@ def tile_work(oracle, scene, mat, sky, W, H, bounces, tile_step=1, tile_first=0)
     pad[:H, :W] = px
     tiles = pad.reshape(gy, 8, gx, 8).sum(axis=(1, 3))
     return tiles[tile_first::tile_step].ravel()
+
+
+# ---- the sphere dispatcher restated: which kernel form renders a sphere frame (tests/test_sphere_forms_gpu.py) ----
+KID_LITERAL, KID_BRUTE_SINGLE, KID_BRUTE_PIPELINE = 1, 2, 3              # include/rt355.h: rt_kernel_id
+KID_HIERARCHY_8, KID_HIERARCHY_12, KID_HIERARCHY_16, KID_HIERARCHY_GLOBAL = 4, 5, 6, 7
+LDS_CAP = 160 * 1024                                                      # rt_kernels.hip: kLdsCap
+
+
+def filter_plan(scene, bounces):
+    """(filter_ok, signed_filter) of the library's own rt_plan (rt_api.hip), through the rt_filter_plan export."""
+    import ctypes
+    from compute_raytracer_amd import abi
+    fp = ctypes.POINTER(ctypes.c_float)
+    rec = np.ascontiguousarray(scene.pack_spheres(), np.float32).reshape(-1, 8)
+    p = np.ascontiguousarray(scene.pack_params(bounces), np.float32)
+    ok, sgn = ctypes.c_int(-1), ctypes.c_int(-1)
+    abi.check(abi.load().rt_filter_plan(rec.ctypes.data_as(fp), rec.shape[0], p.ctypes.data_as(fp), ctypes.byref(ok), ctypes.byref(sgn)))
+    return bool(ok.value), int(sgn.value)
+
+
+def hierarchy_nodes(scene):
+    """Inner + leaf node count of the sphere hierarchy the library builds (rt_build_hierarchy: rt_bvh_build, arity 4)."""
+    import ctypes
+    from compute_raytracer_amd import abi
+    rec = np.ascontiguousarray(scene.pack_spheres(), np.float32).reshape(-1, 8)
+    n = rec.shape[0]
+    cap = 2 * n + 64
+    out, link, nodes = np.zeros((cap, 4), np.float32), np.zeros(cap, np.uint32), ctypes.c_uint32(0)
+    abi.check(abi.load().rt_build_hierarchy(rec.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
+                                            link.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cap, ctypes.byref(nodes)))
+    return nodes.value
+
+
+def sky_is_flat(sky):
+    """rt_api.hip rt_enqueue: six 1x1 faces whose first texel has one RGB (face_texel0 leaves alpha out)."""
+    faces = [np.asarray(f) for f in sky.faces]
+    return all(f.shape[:2] == (1, 1) for f in faces) and all(np.array_equal(f[0, 0, :3], faces[0][0, 0, :3]) for f in faces)
+
+
+def bvh_room(n_nodes, waves, entries):
+    """rt_bvh.hip: bvh_lds_l0, bvh_gap_waves, bvh_lds_lists, bvh_list_bytes and launch_bvh's room(), for LDS at address 0."""
+    need = (4 * (n_nodes + 1) + 2) // 3
+    l0 = max(1024, need)
+    l0 = (l0 + 15) & ~15
+    gap = min((l0 - 1024) // 512, waves)
+    lists = 4 * l0 + 16 * ((n_nodes + 4) & ~3)
+    return lists + waves * 128 * (entries + 1) + (waves - gap) * 512
+
+
+def lds_fits(k, nbytes):
+    """rt_bvh.hip lds_fits: k workgroups of `nbytes` each in one CU's 128 granules of 1280 bytes."""
+    return k * ((nbytes + 1279) // 1280) <= 128
+
+
+class SphereForm:
+    """What expected_sphere_form predicts: the rt_kernel_id, the form behind it and its hidden template arguments."""
+    def __init__(self, kernel_id, form, sgn=None, flat=None, cap=None, resolve=False):
+        self.kernel_id, self.form, self.sgn, self.flat, self.cap, self.resolve = kernel_id, form, sgn, flat, cap, resolve
+
+    def __repr__(self):
+        return "SphereForm(%d, %s, sgn=%s, flat=%s, cap=%s, resolve=%s)" % (self.kernel_id, self.form, self.sgn, self.flat, self.cap, self.resolve)
+
+
+def expected_sphere_form(scene, bounces, strict=False, variant=0, sky=None, in_flight=False):
+    """The form rt_enqueue / rt_launch_trace / rt_launch_bvh must give a sphere frame.  in_flight: the library has seen the
+    previous batch of frames in flight on its own streams (rt_wait: pipelined_hint).  None: the frame is refused."""
+    sky = sky if sky is not None else rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA)
+    flat = sky_is_flat(sky)
+    n = len(scene.spheres)
+    n16 = (n + 15) & ~15
+    filter_ok, sgn = filter_plan(scene, bounces)                          # rt_api.hip rt_plan
+    fast = not strict
+    # rt_api.hip rt_enqueue: bvh_from, use_bvh, queue_pipeline, cfg.mode / cfg.variant
+    use_bvh = fast and filter_ok and n > 0 and (variant == 4 or (variant == 0 and n >= (72 if in_flight else 128)))
+    queue = not use_bvh and fast and filter_ok and (variant in (2, 3) or (variant in (0, 4, 5) and n >= 320))
+    if use_bvh:                                                            # rt_bvh.hip launch_bvh
+        nodes = hierarchy_nodes(scene)
+        resolve = not flat                                                 # rt_launch_sky_resolve behind a textured sky
+        for kid, waves, cap, k in ((KID_HIERARCHY_8, 8, 12, 3), (KID_HIERARCHY_12, 12, 12, 2), (KID_HIERARCHY_12, 12, 6, 2)):
+            if lds_fits(k, bvh_room(nodes, waves, cap)):
+                return SphereForm(kid, "bvh%d" % waves, sgn, flat, cap, resolve)
+        for cap in (12, 6):
+            if bvh_room(nodes, 16, cap) <= LDS_CAP:
+                return SphereForm(KID_HIERARCHY_16, "bvh16", sgn, flat, cap, resolve)
+        return SphereForm(KID_HIERARCHY_GLOBAL, "bvh_global", sgn, flat, 8, resolve)
+    if not filter_ok or strict:                                            # rt_kernels.hip launch_strict (literal: no SGN)
+        if n * 48 <= 56 * 1024: return SphereForm(KID_LITERAL, "literal8", None, flat)
+        if n * 48 <= LDS_CAP: return SphereForm(KID_LITERAL, "literal16_w", None, flat)
+        if n * 32 <= LDS_CAP: return SphereForm(KID_LITERAL, "literal16", None, flat)
+        return SphereForm(KID_LITERAL, "literal_global", None, flat)
+    v = 0 if variant in (4, 5) else variant                                # rt_kernels.hip fast_form
+    single = n16 * 60 + 8 * 16 * 256 <= LDS_CAP                           # lds_pixels<8, true, false, true, 16>
+    pipe16 = n16 * 40 + 8 * 16 * 256 <= LDS_CAP                           # lds_paths<8, true, 16> = lds_first<8, true, 8>
+    if 2 * n16 * 16 + 8 * 8 * 256 > LDS_CAP:
+        return SphereForm(KID_BRUTE_SINGLE, "brute_global", sgn, flat)
+    if v == 0 and queue and n >= 320:
+        if pipe16: return SphereForm(KID_BRUTE_PIPELINE, "pipe8", sgn, flat)
+        if n16 * 32 + 16 * 8 * 256 <= LDS_CAP: return SphereForm(KID_BRUTE_PIPELINE, "pipe16", sgn, flat)   # lds_paths<16, false, 8>
+        return SphereForm(KID_BRUTE_PIPELINE, "pipe8_global", sgn, flat)
+    if v in (0, 1):
+        return SphereForm(KID_BRUTE_SINGLE, "single", sgn, flat) if single else None
+    if v == 2:                                                             # lds_pixels<8, true, true, true, 16> and lds_paths<4, true, 16>
+        return SphereForm(KID_BRUTE_PIPELINE, "v2", sgn, flat) if queue and pipe16 and n16 * 40 + 4 * 16 * 256 <= LDS_CAP else None
+    if v == 3:
+        return SphereForm(KID_BRUTE_PIPELINE, "v3", sgn, flat) if queue and pipe16 else None
+    return None
+
+
+def unsigned_ground_spheres(n, seed):
+    """synthetic_spheres with a ground sphere large enough (reach 800 >= 342: 2 reach 7.3e-7 >= 5e-4) that rt_plan takes the
+    unsigned filter (SGN=0); its top still lies at y = 0."""
+    s = synthetic_spheres(n, seed)
+    s[0] = rt.Sphere([0.0, -400.0, 0.0], 400.0, [0.8, 0.8, 0.8])
+    return s
+
+
+def unsigned_tiny_spheres(n, seed):
+    """synthetic_spheres with one radius below 2^-30 (rt_plan: min_radius): SGN=0 in a compact scene."""
+    s = synthetic_spheres(n, seed)
+    s[-1] = rt.Sphere(list(s[-1].center), 2.0 ** -31, list(s[-1].color))
+    return s
+
+
+def beyond_filter_range(spheres, scene_of=None):
+    """The same spheres, camera and light offset beyond 2^20 (rt_plan: filter_ok false): every mode renders them literally."""
+    off = np.array([3.0e6, -2.0e6, 1.5e6])
+    moved = [rt.Sphere(off + np.asarray(s.center, np.float64), s.radius, list(s.color)) for s in spheres]
+    scene = rt.SceneRaytracing().createScene(moved)
+    scene.camera.position = list(off + np.asarray(scene.camera.position, np.float64))
+    scene.camera.update()
+    scene.light.position = list(off + np.asarray(scene.light.position, np.float64))
+    return scene
+
+
+def non_cube_sky(seed):
+    """Six 6x5 faces: neither flat nor seamless (rt_enqueue: sky_seamless = 0)."""
+    return random_sky(seed, w=6, h=5)
+
+
+class SphereCase:
+    """One cell of tests/test_sphere_forms_gpu.py: a scene of `n` spheres (sgn 1: synthetic_spheres; 0: its unsigned twin,
+    `unsigned` = "ground" or "tiny"; far: offset beyond the filter's range), a sky ("flat", "cube": 8x8 random faces,
+    "noncube": 6x5), the mode and variant, and the form (and list capacity) expected_sphere_form must give it.  `beside`:
+    the count on the other side of the nearest LDS boundary and the form it must land in instead (None: refused)."""
+    def __init__(self, name, form, n, sgn, sky, beside, strict=False, variant=0, unsigned="ground", far=False, cap=None,
+                 W=160, H=96, B=4, seed=7):
+        self.name, self.form, self.n, self.sgn, self.sky_kind, self.beside = name, form, n, sgn, sky, beside
+        self.strict, self.variant, self.unsigned, self.far, self.cap = strict, variant, unsigned, far, cap
+        self.W, self.H, self.B, self.seed = W, H, B, seed
+
+    def scene(self, n=None):
+        n = self.n if n is None else n
+        build = synthetic_spheres if self.sgn != 0 else (unsigned_ground_spheres if self.unsigned == "ground" else unsigned_tiny_spheres)
+        spheres = build(n, self.seed)
+        return beyond_filter_range(spheres) if self.far else rt.SceneRaytracing().createScene(spheres)
+
+    def sky(self):
+        if self.sky_kind == "flat": return rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA)
+        return random_sky(self.seed + self.n) if self.sky_kind == "cube" else non_cube_sky(self.seed + self.n)
+
+    def expected(self, n=None, scene=None):
+        return expected_sphere_form(scene if scene is not None else self.scene(n), self.B, self.strict, self.variant, self.sky())
+
+
+def _sphere_cases():
+    cases = []
+    # frame size and bounces per (SGN, sky) cell: ragged widths and heights in half of them
+    frames = {(1, "flat"): (160, 96, 4), (1, "tex"): (157, 91, 5), (0, "flat"): (157, 91, 3), (0, "tex"): (160, 96, 4)}
+    # literal forms (rt_kernels.hip launch_strict; no SGN), strict mode: the last count of each form and the first beyond the 3rd
+    for form, n, beside, skies in (("literal8", 1194, (1195, "literal16_w"), ("flat", "cube")),
+                                   ("literal16_w", 3413, (3414, "literal16"), ("flat", "cube")),
+                                   ("literal16", 5120, (5121, "literal_global"), ("flat", "noncube")),
+                                   ("literal_global", 5121, (5120, "literal16"), ("flat", "cube"))):
+        for sky in skies:
+            W, H, B = frames[(1, "flat" if sky == "flat" else "tex")]
+            cases.append(SphereCase("strict-%s-%s" % (form, sky), form, n, None, sky, beside, strict=True, W=W, H=H, B=B))
+    # ... and the two 16-wave ones in fast mode, for a scene beyond the filter's range (filter_ok false), at their first counts
+    for form, n, beside, sky in (("literal16_w", 1195, (1194, "literal8"), "flat"), ("literal16_w", 1195, (1194, "literal8"), "cube"),
+                                 ("literal16", 3414, (3413, "literal16_w"), "flat"), ("literal16", 3414, (3413, "literal16_w"), "noncube")):
+        W, H, B = frames[(0, "flat" if sky == "flat" else "tex")]
+        cases.append(SphereCase("far-%s-%s" % (form, sky), form, n, None, sky, beside, far=True, W=W, H=H, B=B))
+    # brute-force forms (rt_kernels.hip fast_form) at their LDS limits; hierarchy forms (rt_bvh.hip launch_bvh) at the last
+    # count of each form, counts from expected_sphere_form (tests/test_sphere_forms_cpu.py)
+    brute = (("single", 2176, 1, (2177, None)), ("pipe8", 3264, 5, (3265, "pipe16")), ("pipe16", 4096, 5, (4097, "pipe8_global")),
+             ("pipe8_global", 4608, 5, (4609, "brute_global")), ("brute_global", 4609, 5, (4608, "pipe8_global")),
+             ("v2", 3264, 2, (3265, None)), ("v3", 3264, 3, (3265, None)))
+    bvh = (("bvh8", 12, 1184, (1185, "bvh12", 12)), ("bvh12", 12, 1789, (1790, "bvh12", 6)), ("bvh12", 6, 2106, (2107, "bvh16", 12)),
+           ("bvh16", 12, 4338, (4339, "bvh16", 6)), ("bvh16", 6, 4724, (4725, "bvh_global", 8)), ("bvh_global", 8, 4725, (4724, "bvh16", 6)))
+    rows = [(f, None, n, v, b) for f, n, v, b in brute] + [(f, c, n, 0, b) for f, c, n, b in bvh]
+    for i, (form, cap, n, variant, beside) in enumerate(rows):
+        for sgn in (1, 0):
+            for tex in (False, True):
+                sky = "flat" if not tex else ("cube" if sgn == 1 else "noncube")
+                W, H, B = frames[(sgn, "tex" if tex else "flat")]
+                uns = "ground" if i % 2 == 0 else "tiny"
+                name = "%s%s-sgn%d-%s" % (form, "" if cap is None else "-cap%d" % cap, sgn, sky)
+                cases.append(SphereCase(name, form, n, sgn, sky, beside, variant=variant, unsigned=uns, cap=cap, W=W, H=H, B=B))
+    return cases
+
+
+SPHERE_CASES = _sphere_cases()
+
+
+def crowded_spheres(n, seed, unsigned=False):
+    """n - 1 heavily overlapping spheres in a 5-unit box in front of the reference's camera, over a ground sphere (unsigned: the
+    large one of unsigned_ground_spheres): every primary ray crosses dozens of them, so the hierarchy's candidate lists fill
+    to their last row."""
+    rng = np.random.default_rng(seed)
+    g = rt.Sphere([0.0, -400.0, 0.0], 400.0, [0.8, 0.8, 0.8]) if unsigned else rt.Sphere([0.0, -100.0, 0.0], 100.0, [0.8, 0.8, 0.8])
+    pos = np.stack([rng.uniform(-2.5, 2.5, n - 1), rng.uniform(0.5, 5.5, n - 1), rng.uniform(-12.5, -7.5, n - 1)], axis=1)
+    return [g] + [rt.Sphere(p, float(rng.uniform(0.3, 0.9)), rng.uniform(0.2, 1.0, 3)) for p in pos]
+
+
+# crowded_spheres scenes for the 12- and 16-wave hierarchy forms: (count, form, list capacity, SGN, sky)
+CROWDED_CASES = ((1700, "bvh12", 12, 1, "cube"), (1700, "bvh12", 12, 0, "flat"), (2000, "bvh12", 6, 1, "flat"), (2000, "bvh12", 6, 0, "cube"),
+                 (3000, "bvh16", 12, 1, "flat"), (3000, "bvh16", 12, 0, "noncube"), (4500, "bvh16", 6, 1, "cube"), (4500, "bvh16", 6, 0, "flat"))
+
+
+def crowded_case(n, sgn, sky):
+    scene = rt.SceneRaytracing().createScene(crowded_spheres(n, 5, unsigned=sgn == 0))
+    s = (rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA) if sky == "flat" else random_sky(n) if sky == "cube" else non_cube_sky(n))
+    return scene, s
