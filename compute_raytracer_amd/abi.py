@@ -21,6 +21,7 @@ RT_KERNEL_RAYTRACER = 0
 RT_KERNEL_HEATMAP = 1
 RT_MODE_FAST = 0
 RT_MODE_STRICT = 1
+RT_QUERY_LIMITS = 1      # flags of rt_trace_rays_ex / rt_occluded: ray words 3 and 7 are tmin and tmax
 
 # every symbol include/rt355.h declares (tests check the library exports each of them)
 SYMBOLS = [
@@ -35,6 +36,7 @@ SYMBOLS = [
     "rt_build_id", "rt_kernel_name", "rt_set_comm_timeout",
     "rt_read_pixels_async", "rt_read_pixels_wait", "rt_host_alloc", "rt_host_free",
     "rt_trace_rays", "rt_trace_rays_host", "rt_pick",
+    "rt_trace_rays_ex", "rt_trace_rays_host_ex", "rt_occluded", "rt_occluded_host",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -163,6 +165,10 @@ def load():
         "rt_trace_rays": (ctypes.c_int, [vp, vp, u32, vp, vp]),
         "rt_trace_rays_host": (ctypes.c_int, [vp, vp, u32, vp]),
         "rt_pick": (ctypes.c_int, [vp, vp, u32, vp]),
+        "rt_trace_rays_ex": (ctypes.c_int, [vp, vp, u32, u32, vp, vp]),
+        "rt_trace_rays_host_ex": (ctypes.c_int, [vp, vp, u32, u32, vp]),
+        "rt_occluded": (ctypes.c_int, [vp, vp, u32, u32, vp, vp]),
+        "rt_occluded_host": (ctypes.c_int, [vp, vp, u32, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

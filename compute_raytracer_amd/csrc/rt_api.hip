@@ -1451,9 +1451,17 @@ static int query_prepare(rt_ctx* c, const char* who, hipStream_t s, bool& tri, R
     return RT_OK;
 }
 
-static int query_launch(rt_ctx* c, const float4* rays, float4* hits, uint32_t n, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
-    if (tri) RT_HIP(rt_launch_query_triangles(ts, inst, rays, hits, n, s));
-    else RT_HIP(rt_launch_query_spheres(c->d_records, c->n, rays, hits, n, s));
+// flags (RT_QUERY_LIMITS) or `any` (rt_occluded: `out` is one byte per ray): the limited forms; otherwise rt_trace_rays' own
+static int query_launch(rt_ctx* c, const float4* rays, void* out, uint32_t n, hipStream_t s, bool tri, const RtTriScene& ts, int inst,
+                        uint32_t flags = 0u, bool any = false) {
+    if (!flags && !any) {
+        float4* hits = static_cast<float4*>(out);
+        if (tri) RT_HIP(rt_launch_query_triangles(ts, inst, rays, hits, n, s));
+        else RT_HIP(rt_launch_query_spheres(c->d_records, c->n, rays, hits, n, s));
+    } else {
+        if (tri) RT_HIP(rt_launch_limited_triangles(ts, inst, rays, flags, any, out, n, s));
+        else RT_HIP(rt_launch_limited_spheres(c->d_records, c->n, rays, flags, any, out, n, s));
+    }
     RT_HIP(hipEventRecord(c->ev_query, s));
     c->query_pending = true;
     c->query_last = s;
@@ -1480,38 +1488,69 @@ static int query_stream(rt_ctx* c, hipStream_t& s) {
 
 static_assert(sizeof(rt_hit) == 32, "rt_hit is two float4");
 
-int rt_trace_rays(rt_ctx* c, const float* rays, uint32_t n, rt_hit* hits, void* hip_stream) {
-    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_trace_rays: ctx is NULL");
+// rt_trace_rays_ex / rt_occluded: device memory, on `hip_stream`; `out` holds n rt_hit records, or n bytes when `any`
+static int query_device(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, bool any, void* out, void* hip_stream) {
+    char msg[160];
+    // (the flags first: a pure argument check, whatever the context)
+    if (flags & ~RT_QUERY_LIMITS) { std::snprintf(msg, sizeof msg, "%s: unknown flag bits 0x%x", who, flags); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
     if (n == 0) return RT_OK;
-    if (!rays || !hits) return fail(RT_ERR_INVALID_ARG, "rt_trace_rays: NULL argument");
-    if ((reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) % 16u)
-        return fail(RT_ERR_INVALID_ARG, "rt_trace_rays: rays and hits must be 16-byte aligned");
+    if (!rays || !out) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if ((reinterpret_cast<uintptr_t>(rays) | (any ? (uintptr_t)0 : reinterpret_cast<uintptr_t>(out))) % 16u) {
+        std::snprintf(msg, sizeof msg, "%s: %s must be 16-byte aligned", who, any ? "rays" : "rays and hits");
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
     const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     bool tri;
     int inst;
     RtTriScene ts;
-    { int rc = query_prepare(c, "rt_trace_rays", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    return query_launch(c, reinterpret_cast<const float4*>(rays), reinterpret_cast<float4*>(hits), n, s, tri, ts, inst);
+    { int rc = query_prepare(c, who, s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    return query_launch(c, reinterpret_cast<const float4*>(rays), out, n, s, tri, ts, inst, flags, any);
 }
 
-int rt_trace_rays_host(rt_ctx* c, const float* rays, uint32_t n, rt_hit* hits) {
-    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_trace_rays_host: ctx is NULL");
+// rt_trace_rays_host_ex / rt_occluded_host: host memory, staged through the context's query buffers, synchronous
+static int query_host(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, bool any, void* out) {
+    char msg[160];
+    // (the flags first: a pure argument check, whatever the context)
+    if (flags & ~RT_QUERY_LIMITS) { std::snprintf(msg, sizeof msg, "%s: unknown flag bits 0x%x", who, flags); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
     if (n == 0) return RT_OK;
-    if (!rays || !hits) return fail(RT_ERR_INVALID_ARG, "rt_trace_rays_host: NULL argument");
+    if (!rays || !out) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
     hipStream_t s;
     { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
     bool tri;
     int inst;
     RtTriScene ts;
-    { int rc = query_prepare(c, "rt_trace_rays_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    const size_t bytes = (size_t)n * 32u;
+    { int rc = query_prepare(c, who, s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    const size_t bytes = (size_t)n * 32u, out_bytes = any ? (size_t)n : bytes;
     { int rc = grow_staging(c->d_qrays, bytes); if (rc != RT_OK) return rc; }
-    { int rc = grow_staging(c->d_qhits, bytes); if (rc != RT_OK) return rc; }
+    { int rc = grow_staging(c->d_qhits, out_bytes); if (rc != RT_OK) return rc; }
     RT_HIP(hipMemcpyAsync(c->d_qrays.p, rays, bytes, hipMemcpyHostToDevice, s));
-    { int rc = query_launch(c, static_cast<const float4*>(c->d_qrays.p), static_cast<float4*>(c->d_qhits.p), n, s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    RT_HIP(hipMemcpyAsync(hits, c->d_qhits.p, bytes, hipMemcpyDeviceToHost, s));
+    { int rc = query_launch(c, static_cast<const float4*>(c->d_qrays.p), c->d_qhits.p, n, s, tri, ts, inst, flags, any); if (rc != RT_OK) return rc; }
+    RT_HIP(hipMemcpyAsync(out, c->d_qhits.p, out_bytes, hipMemcpyDeviceToHost, s));
     RT_HIP(hipStreamSynchronize(s));
     return RT_OK;
+}
+
+int rt_trace_rays_ex(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, rt_hit* hits, void* hip_stream) {
+    return query_device("rt_trace_rays_ex", c, rays, n, flags, false, hits, hip_stream);
+}
+int rt_trace_rays_host_ex(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, rt_hit* hits) {
+    return query_host("rt_trace_rays_host_ex", c, rays, n, flags, false, hits);
+}
+int rt_occluded(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, uint8_t* occluded, void* hip_stream) {
+    return query_device("rt_occluded", c, rays, n, flags, true, occluded, hip_stream);
+}
+int rt_occluded_host(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, uint8_t* occluded) {
+    return query_host("rt_occluded_host", c, rays, n, flags, true, occluded);
+}
+
+int rt_trace_rays(rt_ctx* c, const float* rays, uint32_t n, rt_hit* hits, void* hip_stream) {
+    return query_device("rt_trace_rays", c, rays, n, 0u, false, hits, hip_stream);
+}
+
+int rt_trace_rays_host(rt_ctx* c, const float* rays, uint32_t n, rt_hit* hits) {
+    return query_host("rt_trace_rays_host", c, rays, n, 0u, false, hits);
 }
 
 int rt_pick(rt_ctx* c, const uint32_t* xy, uint32_t n, rt_hit* hits) {

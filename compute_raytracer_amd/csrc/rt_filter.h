@@ -9,16 +9,17 @@ namespace rtk {
 // ---- literal ray-sphere test (HK:308-318) ------------------------------------------------------------
 // SHORTCUT: b >= 0 makes (-b - sqrt(disc)) <= 0, so t <= 0 fails `t > tMin`; skipping the
 // square root and the division then is exact.  The strict kernel keeps the literal form.
-template <bool SHORTCUT>
+// LIMITS (ray queries with RT_QUERY_LIMITS): `tmin` replaces the 0.001 of HK:318; the caller starts `nearest` at tmax.
+template <bool SHORTCUT, bool LIMITS = false>
 __device__ __forceinline__ void exact_full(v3 center, float r2, int s, v3 o, v3 d, float fa, float ta,
-                                           float& nearest, int& idx) {
+                                           float& nearest, int& idx, float tmin = 0.0f) {
     const v3 oc = sub(o, center);
     const float b = 2.0f * dot(d, oc);              // HK:309
     const float c = dot(oc, oc) - r2;               // HK:310
     const float disc = b * b - fa * c;              // HK:311
     if (disc > 0.0f && (!SHORTCUT || b < 0.0f)) {   // HK:316
         const float t = (-b - sqrtf(disc)) / ta;    // HK:317
-        if (t > 0.001f && t < nearest) {            // HK:318 with tMin/tMax of RK:315
+        if (t > (LIMITS ? tmin : 0.001f) && t < nearest) {   // HK:318 with tMin/tMax of RK:315
             nearest = t;
             idx = s;
         }

@@ -14,6 +14,12 @@
 //     (any sphere count).  Not the bounding-sphere hierarchy: its no-lost-hit proof (rt_bvh.hip) assumes unit directions and
 //     origins within rt_plan's reach, and caller rays promise neither.
 //   pick_rays: the primary ray of pixel (x, y) (RK:76-86, rt_device.h: primary_dir) into a ray buffer.
+// The limited and occlusion forms (rt_trace_rays_ex, rt_occluded): the same walks over (tmin, tmax), from ray words 3 and 7
+// under RT_QUERY_LIMITS and (0.001, 9999) otherwise -- the literal bounds, so a lane without limits does what the forms above do.
+//   limited_triangles<..., ANY>: trace_tlas<LIMITS, ANY>; the occlusion form (ANY) leaves both loops at the first accepted
+//     triangle and writes one byte: no normal, no triangle lookup.  The same LDS as query_triangles.
+//   limited_spheres / occlude_spheres: the literal loop with exact_full<LIMITS>.  In occlude_spheres a lane stops testing at its
+//     first accepted sphere, and the workgroup stops staging chunks once none of its lanes is still searching.
 #include <type_traits>
 
 #include "rt_device.h"
@@ -109,6 +115,125 @@ __global__ __launch_bounds__(kQueryThreads) void query_spheres(const float* __re
     store_hit(hits, i, nearest, 0.0f, 0.0f, idx, -1, nrm);
 }
 
+// ---- RT_QUERY_LIMITS and occlusion -------------------------------------------------------------------------------------------
+// (tmin, tmax) of ray i: words 3 and 7 under RT_QUERY_LIMITS, else the reference's 0.001 and 9999
+__device__ __forceinline__ void load_ray_limits(const float4* __restrict__ rays, size_t i, bool limits, v3& o, v3& d,
+                                                float& tmin, float& tmax) {
+    const float4 a = rays[2u * i], b = rays[2u * i + 1u];
+    o = V(a.x, a.y, a.z);
+    d = V(b.x, b.y, b.z);
+    tmin = limits ? a.w : 0.001f;
+    tmax = limits ? b.w : 9999.0f;
+}
+
+// query_triangles over (tmin, tmax); ANY: rt_occluded (one byte per ray in `occ`), else rt_hit records in `hits`
+template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST, bool ANY>
+__global__ __launch_bounds__(kQueryThreads) void limited_triangles(const RtTriScene T, const float4* __restrict__ rays, uint32_t flags,
+                                                                   float4* __restrict__ hits, uint8_t* __restrict__ occ, uint32_t n) {
+    typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
+    constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
+    __shared__ STK tstacks[kStack * kQueryThreads];
+    __shared__ BSTK bstacks[kStack * kQueryThreads];
+    __shared__ float4 s_nodes[2 * NODES];
+    __shared__ float s_blas[20 * BLAS];
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);
+    const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
+    if (i >= n) return;
+    v3 o, d;
+    float tmin, tmax;
+    load_ray_limits(rays, i, (flags & RT_QUERY_LIMITS) != 0u, o, d, tmin, tmax);
+    RtTriScene Tq = T;                             // (as in query_triangles)
+    if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
+    float traces = 0.0f;
+    const TriHit h = trace_tlas<false, STK, PACKED, PAIRS, P16, kStack, /*LIMITS=*/true, ANY>(
+        Tq, L, o, d, tstacks + threadIdx.x, bstacks + threadIdx.x, kQueryThreads, traces, tmin, tmax);
+    if (ANY) { occ[i] = h.tri >= 0 ? 1u : 0u; return; }
+    if (h.tri < 0) { store_miss(hits, i); return; }
+    const uint32_t bi = (uint32_t)h.blas;
+    const float* m = bi < L.n_blas ? L.blas + 20u * bi : T.blas + 20u * (size_t)bi;
+    const v3 nrm = hit_normal(T, h, m);
+    store_hit(hits, i, h.t, h.u, h.v, (int)tri_of(T, h.tri), h.blas, nrm);
+}
+
+// query_spheres over (tmin, tmax): the running nearest hit starts at tmax
+__global__ __launch_bounds__(kQueryThreads) void limited_spheres(const float* __restrict__ records, uint32_t n_spheres,
+                                                                 const float4* __restrict__ rays, uint32_t flags,
+                                                                 float4* __restrict__ hits, uint32_t n) {
+    __shared__ float4 s_geo[kSphereChunk];
+    const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
+    const bool live = i < n;                       // every lane stages: no return before the last barrier
+    v3 o = V(0.0f, 0.0f, 0.0f), d = V(0.0f, 0.0f, 0.0f);
+    float tmin = 0.001f, tmax = 9999.0f;
+    if (live) load_ray_limits(rays, i, (flags & RT_QUERY_LIMITS) != 0u, o, d, tmin, tmax);
+    const float a = dot(d, d);                     // HK:308
+    const float fa = 4.0f * a;                     // the (4*a) of HK:311
+    const float ta = 2.0f * a;                     // HK:317
+    float nearest = tmax;
+    int idx = -1;
+    for (uint32_t base = 0; base < n_spheres; base += kSphereChunk) {
+        const uint32_t m = n_spheres - base < kSphereChunk ? n_spheres - base : kSphereChunk;
+        __syncthreads();                           // the previous chunk is done with
+        for (uint32_t k = threadIdx.x; k < m; k += kQueryThreads) {
+            const float4* r = reinterpret_cast<const float4*>(records + 8u * ((size_t)base + k));
+            const float4 c = r[0], w = r[1];
+            s_geo[k] = make_float4(c.x, c.y, c.z, w.w * w.w);       // radius * radius (HK:310)
+        }
+        __syncthreads();
+        if (live) {
+            for (uint32_t k = 0; k < m; ++k) {
+                const float4 g = s_geo[k];
+                exact_full<false, true>(V(g.x, g.y, g.z), g.w, (int)(base + k), o, d, fa, ta, nearest, idx, tmin);
+            }
+        }
+    }
+    if (!live) return;
+    if (idx < 0) { store_miss(hits, i); return; }
+    const float* s = records + 8u * (size_t)idx;
+    const v3 position = add(o, scale(nearest, d));                     // HK:319
+    const v3 nrm = normalize(sub(position, V(s[0], s[1], s[2])));       // HK:320
+    store_hit(hits, i, nearest, 0.0f, 0.0f, idx, -1, nrm);
+}
+
+// limited_spheres up to the first accepted sphere: that acceptance is the nearest search's first too (nearest is still tmax),
+// so a lane is occluded exactly when limited_spheres would report a hit
+__global__ __launch_bounds__(kQueryThreads) void occlude_spheres(const float* __restrict__ records, uint32_t n_spheres,
+                                                                 const float4* __restrict__ rays, uint32_t flags,
+                                                                 uint8_t* __restrict__ occ, uint32_t n) {
+    __shared__ float4 s_geo[kSphereChunk];
+    const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
+    const bool live = i < n;                       // every lane stages: no return before the last barrier
+    v3 o = V(0.0f, 0.0f, 0.0f), d = V(0.0f, 0.0f, 0.0f);
+    float tmin = 0.001f, tmax = 9999.0f;
+    if (live) load_ray_limits(rays, i, (flags & RT_QUERY_LIMITS) != 0u, o, d, tmin, tmax);
+    const float a = dot(d, d);                     // HK:308
+    const float fa = 4.0f * a;                     // the (4*a) of HK:311
+    const float ta = 2.0f * a;                     // HK:317
+    float nearest = tmax;
+    int idx = -1;
+    bool searching = live;
+    for (uint32_t base = 0; base < n_spheres; base += kSphereChunk) {
+        // the previous chunk is done with -- and when no lane of the workgroup still searches, no chunk more is staged (the
+        // barrier's answer is the same in every lane: all of them leave together)
+        if (!__syncthreads_or(searching)) break;
+        const uint32_t m = n_spheres - base < kSphereChunk ? n_spheres - base : kSphereChunk;
+        for (uint32_t k = threadIdx.x; k < m; k += kQueryThreads) {
+            const float4* r = reinterpret_cast<const float4*>(records + 8u * ((size_t)base + k));
+            const float4 c = r[0], w = r[1];
+            s_geo[k] = make_float4(c.x, c.y, c.z, w.w * w.w);       // radius * radius (HK:310)
+        }
+        __syncthreads();
+        if (searching) {
+            for (uint32_t k = 0; k < m; ++k) {
+                const float4 g = s_geo[k];
+                exact_full<false, true>(V(g.x, g.y, g.z), g.w, (int)(base + k), o, d, fa, ta, nearest, idx, tmin);
+                if (idx >= 0) { searching = false; break; }
+            }
+        }
+    }
+    if (!live) return;
+    occ[i] = idx >= 0 ? 1u : 0u;
+}
+
 // the primary ray of pixel (x, y) (RK:76-86): the ray that pixel of the next frame starts with
 __global__ __launch_bounds__(256) void pick_rays(const RtFrameArgs A, const uint32_t* __restrict__ xy, float4* __restrict__ rays, uint32_t n) {
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
@@ -131,6 +256,28 @@ static void launch_qt_walk(const RtTriScene& t, const float4* rays, float4* hits
     else                                   launch_qt<uint32_t, false, false, false, INST>(t, rays, hits, n, s);
 }
 
+template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST, bool ANY>
+static void launch_lt(const RtTriScene& t, const float4* rays, uint32_t flags, void* out, uint32_t n, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)(((size_t)n + kQueryThreads - 1u) / kQueryThreads);
+    hipLaunchKernelGGL((limited_triangles<STK, PACKED, PAIRS, P16, INST, ANY>), dim3(blocks), dim3(kQueryThreads), 0, s, t, rays, flags,
+                       ANY ? nullptr : static_cast<float4*>(out), ANY ? static_cast<uint8_t*>(out) : nullptr, n);
+}
+template <bool INST, bool ANY>
+static void launch_lt_walk(const RtTriScene& t, const float4* rays, uint32_t flags, void* out, uint32_t n, hipStream_t s) {
+    if (t.n_nodes <= 65536u && t.packed_ok) launch_lt<uint16_t, true, false, false, INST, ANY>(t, rays, flags, out, n, s);
+    else if (t.n_nodes <= 65536u)          launch_lt<uint16_t, false, false, false, INST, ANY>(t, rays, flags, out, n, s);
+    else                                   launch_lt<uint32_t, false, false, false, INST, ANY>(t, rays, flags, out, n, s);
+}
+// the forms of rt_launch_query_triangles
+template <bool ANY>
+static void launch_lt_form(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, void* out, uint32_t n, hipStream_t s) {
+    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= kWideBlas;
+    if (pairs && t.p16_ok) launch_lt<uint16_t, true, true, true, true, ANY>(t, rays, flags, out, n, s);
+    else if (pairs)        launch_lt<uint16_t, true, true, false, true, ANY>(t, rays, flags, out, n, s);
+    else if (inst)         launch_lt_walk<true, ANY>(t, rays, flags, out, n, s);
+    else                   launch_lt_walk<false, ANY>(t, rays, flags, out, n, s);
+}
+
 }  // namespace rtk
 
 hipError_t rt_launch_query_triangles(const RtTriScene& t, int inst, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
@@ -148,6 +295,25 @@ hipError_t rt_launch_query_spheres(const float* records, uint32_t n_spheres, con
     if (n == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
     hipLaunchKernelGGL(rtk::query_spheres, dim3(blocks), dim3(rtk::kQueryThreads), 0, s, records, n_spheres, rays, hits, n);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_limited_triangles(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, bool any, void* out,
+                                       uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (any) rtk::launch_lt_form<true>(t, inst, rays, flags, out, n, s);
+    else     rtk::launch_lt_form<false>(t, inst, rays, flags, out, n, s);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_limited_spheres(const float* records, uint32_t n_spheres, const float4* rays, uint32_t flags, bool any, void* out,
+                                     uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
+    if (any) hipLaunchKernelGGL(rtk::occlude_spheres, dim3(blocks), dim3(rtk::kQueryThreads), 0, s, records, n_spheres, rays, flags,
+                                static_cast<uint8_t*>(out), n);
+    else     hipLaunchKernelGGL(rtk::limited_spheres, dim3(blocks), dim3(rtk::kQueryThreads), 0, s, records, n_spheres, rays, flags,
+                                static_cast<float4*>(out), n);
     return hipGetLastError();
 }
 

@@ -113,8 +113,10 @@ __device__ __forceinline__ uint32_t tri_of(const RtTriScene& T, int slot) {
 // RK:344-381, up to the acceptance test; normal / uv / colour are formed later for the winner.
 // `slot` is the position in the triangle lookup table (RK:314: triangles[u32(triangleLookup[i + left])]); the three
 // corners of that triangle come from T.corners, the library's own compact copy in lookup order (rt_tri_corners below).
+// LIMITS (ray queries with RT_QUERY_LIMITS): `tMin` replaces the reference's 0.001.
+template <bool LIMITS = false>
 __device__ __forceinline__ bool hit_triangle(const RtTriScene& T, uint32_t slot, v3 o, v3 d, float tMax,
-                                             float& t_out, float& u_out, float& v_out) {
+                                             float& t_out, float& u_out, float& v_out, float tMin = 0.0f) {
     const float4* tr = T.corners + 3u * (size_t)slot;
     const float4 A = tr[0], B = tr[1], C = tr[2];
     const v3 cornerA = V(A.x, A.y, A.z);
@@ -133,7 +135,7 @@ __device__ __forceinline__ bool hit_triangle(const RtTriScene& T, uint32_t slot,
     const float t = invDet * dot(edge2, sCrossEdge1);               // RK:377
     u = u * invDet;                                                 // RK:378
     v = v * invDet;                                                 // RK:379
-    if (t > 0.001f && t < tMax) {                                   // RK:380 (tMin 0.001, RK:315)
+    if (t > (LIMITS ? tMin : 0.001f) && t < tMax) {                 // RK:380 (tMin 0.001, RK:315)
         t_out = t; u_out = u; v_out = v;
         return true;
     }
@@ -154,10 +156,12 @@ __device__ __forceinline__ bool hit_triangle(const RtTriScene& T, uint32_t slot,
 // P16 (with PAIRS, scenes whose leaves hold at most three triangles and whose pair records and lookup slots number at most
 // 16,384 -- what the reference's builder makes of meshes up to that size): a stack entry is (count << 14 | x) in TWO bytes;
 // both stacks, the staged heads and the instance records then take 7,616 bytes of LDS per wave and a fifth wave per SIMD fits.
-template <bool COUNT, typename STK, bool PACKED, bool PAIRS = false, bool P16 = false>
+// LIMITS: `tmin` replaces 0.001 in the triangle test (ray queries, RT_QUERY_LIMITS).  ANY: the walk ends at the first accepted
+// triangle (occlusion queries); up to that step it is the nearest-hit walk, step for step.
+template <bool COUNT, typename STK, bool PACKED, bool PAIRS = false, bool P16 = false, bool LIMITS = false, bool ANY = false>
 __device__ __forceinline__ void trace_blas(const RtTriScene& T, const TriLds& L, uint32_t bi, v3 o, v3 d, float& nearest,
                                            TriHit& hit, typename std::conditional<PACKED && !P16, uint32_t, STK>::type* stack,
-                                           uint32_t stride, float& traces) {
+                                           uint32_t stride, float& traces, float tmin = 0.0f) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     auto pack16 = [](uint32_t m) -> uint32_t { return ((m >> 16) << 14) | (m & 0x3FFFu); };
     auto unpack16 = [](uint32_t e) -> uint32_t { return ((e >> 14) << 16) | (e & 0x3FFFu); };
@@ -212,9 +216,10 @@ __device__ __forceinline__ void trace_blas(const RtTriScene& T, const TriLds& L,
                     if (li >= T.n_tri_lookup) li = T.n_tri_lookup - 1u;
                     if (COUNT) traces += 1.0f;                      // HK:279
                     float t, u, v;
-                    if (hit_triangle(T, li, oo, od, pNearest, t, u, v)) {   // RK:312-321
+                    if (hit_triangle<LIMITS>(T, li, oo, od, pNearest, t, u, v, tmin)) {   // RK:312-321
                         pNearest = t;
                         hit.t = t; hit.u = u; hit.v = v; hit.tri = (int)li; hit.blas = (int)bi;
+                        if (ANY) { nearest = t; return; }
                     }
                 }
                 if (psp == 0u) break;                               // RK:324
@@ -267,9 +272,10 @@ __device__ __forceinline__ void trace_blas(const RtTriScene& T, const TriLds& L,
                 if (li >= T.n_tri_lookup) li = T.n_tri_lookup - 1u;  // RK:314: the lookup itself is folded into T.corners
                 if (COUNT) traces += 1.0f;                          // HK:279
                 float t, u, v;
-                if (hit_triangle(T, li, oo, od, blasNearest, t, u, v)) {   // RK:312-321
+                if (hit_triangle<LIMITS>(T, li, oo, od, blasNearest, t, u, v, tmin)) {   // RK:312-321
                     blasNearest = t;
                     hit.t = t; hit.u = u; hit.v = v; hit.tri = (int)li; hit.blas = (int)bi;
+                    if (ANY) { nearest = t; return; }
                 }
             }
             if (sp == 0u) break;                                    // RK:324
@@ -282,11 +288,15 @@ __device__ __forceinline__ void trace_blas(const RtTriScene& T, const TriLds& L,
 }
 
 // RK:168-244 traceTLAS.  tstack / bstack: this lane's two LDS stacks.
-template <bool COUNT, typename STK, bool PACKED, bool PAIRS = false, bool P16 = false, uint32_t TS = kStack>
+// LIMITS: the search is (tmin, tmax) -- tmin replaces 0.001 in the triangle test and the running nearest hit starts at tmax
+// instead of 9999; box pruning is the reference's.  ANY: return at the first accepted triangle (see trace_blas).
+template <bool COUNT, typename STK, bool PACKED, bool PAIRS = false, bool P16 = false, uint32_t TS = kStack, bool LIMITS = false,
+          bool ANY = false>
 __device__ __forceinline__ TriHit trace_tlas(const RtTriScene& T, const TriLds& L, v3 o, v3 d, STK* tstack,
-                                             typename std::conditional<PACKED && !P16, uint32_t, STK>::type* bstack, uint32_t stride, float& traces) {
+                                             typename std::conditional<PACKED && !P16, uint32_t, STK>::type* bstack, uint32_t stride, float& traces,
+                                             float tmin = 0.0f, float tmax = 0.0f) {
     TriHit hit; hit.t = 0.0f; hit.u = hit.v = 0.0f; hit.tri = -1; hit.blas = -1;   // RK:170-171
-    float nearest = 9999.0f;                                        // RK:172
+    float nearest = LIMITS ? tmax : 9999.0f;                        // RK:172
     const v3 inv = V(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     NodeR node = load_node_head(T, L, 0u);                          // RK:175
     uint32_t sp = 0;
@@ -320,7 +330,8 @@ __device__ __forceinline__ TriHit trace_tlas(const RtTriScene& T, const TriLds& 
                 if (li >= T.n_blas_lookup) li = T.n_blas_lookup - 1u;
                 uint32_t bi = u32f(li < L.n_lookup ? L.blas[20u * li + 19u] : T.blas_lookup[li]);   // RK:223
                 if (bi >= T.n_blas) bi = T.n_blas - 1u;
-                trace_blas<COUNT, STK, PACKED, PAIRS, P16>(T, L, bi, o, d, nearest, hit, bstack, stride, traces);   // RK:221-230
+                trace_blas<COUNT, STK, PACKED, PAIRS, P16, LIMITS, ANY>(T, L, bi, o, d, nearest, hit, bstack, stride, traces, tmin);   // RK:221-230
+                if (ANY && hit.tri >= 0) return hit;
             }
             if (sp == 0u) break;                                    // RK:233
             sp -= 1u;

@@ -61,4 +61,9 @@ hipError_t rt_launch_tri_corners(float4* out, const float* tri, const float* loo
 // inst: the instance data travels in t.inst (stage_head<..., true>), as for the small forms; t.pairs only with inst.
 hipError_t rt_launch_query_triangles(const RtTriScene& t, int inst, const float4* rays, float4* hits, uint32_t n, hipStream_t s);
 hipError_t rt_launch_query_spheres(const float* records, uint32_t n_spheres, const float4* rays, float4* hits, uint32_t n, hipStream_t s);
+// RT_QUERY_LIMITS in `flags`: (tmin, tmax) from ray words 3 and 7.  any: one byte per ray (rt_occluded), else rt_hit records
+hipError_t rt_launch_limited_triangles(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, bool any, void* out,
+                                       uint32_t n, hipStream_t s);
+hipError_t rt_launch_limited_spheres(const float* records, uint32_t n_spheres, const float4* rays, uint32_t flags, bool any, void* out,
+                                     uint32_t n, hipStream_t s);
 hipError_t rt_launch_pick_rays(const RtFrameArgs& a, const uint32_t* xy, float4* rays, uint32_t n, hipStream_t s);   // xy: [n][2] u32

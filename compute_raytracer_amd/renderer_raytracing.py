@@ -154,15 +154,51 @@ class RendererRaytracing:
         abi.check(self._lib.rt_read_pixels_wait(self._ctx), self._ctx)
 
     # ---- ray queries: the nearest hit of the host's rays (rt_trace_rays / rt_trace_rays_host / rt_pick) ----------------------
-    def trace_rays(self, origins, directions=None, out=None):
+    def trace_rays(self, origins, directions=None, out=None, tmin=None, tmax=None, limits=False):
         """Nearest hit of each ray against the scene the next frame would render (recalculateScene() first, as render() does).
 
         numpy: origins and directions (n, 3) -> dict of numpy arrays t, u, v, prim, instance (n,) and normal (n, 3), through
         rt_trace_rays_host.  torch: `origins` is a float32 (n, 8) tensor {origin, -, dir, -} on this renderer's device and
         `directions` is None -> an (n, 8) float32 tensor of rt_hit records (prim / instance as int32 bits: .view(torch.int32)),
-        or `out`, enqueued through rt_trace_rays on torch.cuda.current_stream()."""
+        or `out`, enqueued through rt_trace_rays on torch.cuda.current_stream().
+
+        Limits (RT_QUERY_LIMITS, rt_trace_rays_ex): numpy -- `tmin` / `tmax`, each a scalar or an (n,) array; one of them given,
+        the other is the reference's (0.001 or 9999).  torch -- `limits=True` reads words 3 and 7 of the (n, 8) tensor."""
         if type(origins).__module__.split(".")[0] == "torch":
-            return self._trace_rays_torch(origins, directions, out)
+            if tmin is not None or tmax is not None:
+                raise ValueError("trace_rays: with a tensor the limits are words 3 and 7 of the rays (limits=True)")
+            return self._trace_rays_torch(origins, directions, out, abi.RT_QUERY_LIMITS if limits else 0, False)
+        if limits:
+            raise ValueError("trace_rays: limits=True is for (n, 8) tensors; numpy rays take tmin / tmax")
+        flags = abi.RT_QUERY_LIMITS if (tmin is not None or tmax is not None) else 0
+        rays = self._pack_rays(origins, directions, 0.001 if tmin is None else tmin, 9999.0 if tmax is None else tmax)
+        self.recalculateScene()
+        hits = np.zeros(rays.shape[0], dtype=abi.HIT_DTYPE)
+        if flags:
+            abi.check(self._lib.rt_trace_rays_host_ex(self._ctx, rays.ctypes.data, rays.shape[0], flags, hits.ctypes.data), self._ctx)
+        else:
+            abi.check(self._lib.rt_trace_rays_host(self._ctx, rays.ctypes.data, rays.shape[0], hits.ctypes.data), self._ctx)
+        return self._hit_dict(hits)
+
+    def occluded(self, origins, directions=None, tmin=0.001, tmax=9999.0, out=None):
+        """Whether anything blocks each ray within (tmin, tmax) (rt_occluded): exactly where trace_rays with the same limits
+        reports a hit.  numpy: origins and directions (n, 3), tmin / tmax scalars or (n,) arrays -> an (n,) bool array, through
+        rt_occluded_host.  torch: a float32 (n, 8) tensor {origin, tmin, dir, tmax} (tmin / tmax are then words 3 and 7; the
+        keywords must stay at their defaults) -> an (n,) uint8 tensor, or `out`, on torch.cuda.current_stream()."""
+        if type(origins).__module__.split(".")[0] == "torch":
+            if tmin != 0.001 or tmax != 9999.0:
+                raise ValueError("occluded: with a tensor the limits are words 3 and 7 of the rays")
+            return self._trace_rays_torch(origins, directions, out, abi.RT_QUERY_LIMITS, True)
+        rays = self._pack_rays(origins, directions, tmin, tmax)
+        self.recalculateScene()
+        occ = np.zeros(rays.shape[0], dtype=np.uint8)
+        abi.check(self._lib.rt_occluded_host(self._ctx, rays.ctypes.data, rays.shape[0], abi.RT_QUERY_LIMITS, occ.ctypes.data),
+                  self._ctx)
+        return occ.astype(bool)
+
+    @staticmethod
+    def _pack_rays(origins, directions, tmin, tmax):
+        """(n, 8) float32 rays {origin, tmin, dir, tmax}"""
         o = np.asarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.asarray(directions, dtype=np.float32).reshape(-1, 3)
         if o.shape != d.shape:
@@ -170,20 +206,28 @@ class RendererRaytracing:
         rays = np.zeros((o.shape[0], 8), dtype=np.float32)
         rays[:, 0:3] = o
         rays[:, 4:7] = d
-        self.recalculateScene()
-        hits = np.zeros(o.shape[0], dtype=abi.HIT_DTYPE)
-        abi.check(self._lib.rt_trace_rays_host(self._ctx, rays.ctypes.data, rays.shape[0], hits.ctypes.data), self._ctx)
-        return self._hit_dict(hits)
+        for word, lim in ((3, tmin), (7, tmax)):
+            lim = np.asarray(lim, dtype=np.float32)
+            if lim.ndim > 1 or (lim.ndim == 1 and lim.shape[0] != o.shape[0]):
+                raise ValueError("trace_rays: a limit is a scalar or an (n,) array")
+            rays[:, word] = lim
+        return rays
 
-    def _trace_rays_torch(self, rays, directions, out):
+    def _trace_rays_torch(self, rays, directions, out, flags, occlusion):
         import torch
+        name = "occluded" if occlusion else "trace_rays"
         if directions is not None:
-            raise ValueError("trace_rays: a tensor argument is the (n, 8) ray buffer itself")
+            raise ValueError("%s: a tensor argument is the (n, 8) ray buffer itself" % name)
         if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("trace_rays: rays must be a contiguous float32 (n, 8) tensor")
+            raise ValueError("%s: rays must be a contiguous float32 (n, 8) tensor" % name)
         if rays.device.type != "cuda" or rays.device.index != self.device:
-            raise ValueError("trace_rays: rays must live on cuda:%d, this renderer's device" % self.device)
-        if out is None:
+            raise ValueError("%s: rays must live on cuda:%d, this renderer's device" % (name, self.device))
+        if occlusion:
+            if out is None:
+                out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
+            elif out.dtype != torch.uint8 or tuple(out.shape) != (rays.shape[0],) or not out.is_contiguous() or out.device != rays.device:
+                raise ValueError("occluded: out must be a contiguous uint8 (n,) tensor on the rays' device")
+        elif out is None:
             out = torch.empty((rays.shape[0], 8), dtype=torch.float32, device=rays.device)
         elif out.element_size() != 4 or tuple(out.shape) != (rays.shape[0], 8) or not out.is_contiguous() or out.device != rays.device:
             raise ValueError("trace_rays: out must be a contiguous 32-bit (n, 8) tensor on the rays' device")
@@ -197,8 +241,14 @@ class RendererRaytracing:
                 self._query_stream = torch.cuda.Stream(rays.device)
             run = self._query_stream
             run.wait_stream(cur)
-        abi.check(self._lib.rt_trace_rays(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0],
-                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(run.cuda_stream)), self._ctx)
+        args = (self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0])
+        tail = (ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(run.cuda_stream))
+        if occlusion:
+            abi.check(self._lib.rt_occluded(*args, flags, *tail), self._ctx)
+        elif flags:
+            abi.check(self._lib.rt_trace_rays_ex(*args, flags, *tail), self._ctx)
+        else:
+            abi.check(self._lib.rt_trace_rays(*args, *tail), self._ctx)
         if run is not cur:
             cur.wait_stream(run)
         return out

@@ -266,7 +266,8 @@ int rt_device_pixels(rt_ctx* ctx, void** out_ptr, size_t* out_bytes);
 
 /* ---- ray queries: the nearest hit of rays the host supplies (RK:168-244 / RK:311-322 without the shading) ------------------ */
 
-/* One ray: 8 f32 = {origin.xyz, reserved, dir.xyz, reserved}.  Reserved words are ignored (kept for a later per-ray limit).
+/* One ray: 8 f32 = {origin.xyz, tmin, dir.xyz, tmax}.  Words 3 and 7 are read only under RT_QUERY_LIMITS (rt_trace_rays_ex,
+ * rt_occluded); everywhere else they are ignored.
  * dir need not be unit length; t is in units of |dir|, as in the reference's arithmetic. */
 typedef struct rt_hit {
     float t;          /* nearest hit, RK:168-244 traceTLAS / RK:311-322 over spheres: tMin 0.001, search starts at 9999; -1 on a miss */
@@ -297,6 +298,33 @@ typedef struct rt_hit {
 int rt_trace_rays(rt_ctx* ctx, const float* rays, uint32_t n, rt_hit* hits, void* hip_stream);  /* device memory, async     */
 int rt_trace_rays_host(rt_ctx* ctx, const float* rays, uint32_t n, rt_hit* hits);               /* host memory, synchronous */
 int rt_pick(rt_ctx* ctx, const uint32_t* xy, uint32_t n, rt_hit* hits);                         /* host memory, synchronous */
+
+/* ---- bounded and occlusion queries ---------------------------------------------------------------------------------------- */
+
+/* flags of rt_trace_rays_ex / rt_occluded */
+#define RT_QUERY_LIMITS 1u   /* ray word 3 is tmin, word 7 is tmax */
+
+/* rt_trace_rays_ex / rt_trace_rays_host_ex: rt_trace_rays / rt_trace_rays_host with flags.  rt_occluded / rt_occluded_host: whether
+ * anything blocks each ray: occluded[i] = 1 or 0, one byte per ray.  Memory, streams and the contract of rt_trace_rays above apply
+ * word for word (`rays` 16-byte aligned, `hits` too; `occluded` needs no alignment).  Unknown flag bits: RT_ERR_INVALID_ARG.
+ *
+ * Limits.
+ *   - flags = 0: the search is today's (tmin 0.001, search starts at 9999); words 3 and 7 are ignored, whatever they hold.
+ *   - RT_QUERY_LIMITS: word 3 is tmin and replaces the 0.001 of the acceptance tests (triangles RK:380 `t > tmin && t < tMax`,
+ *     spheres HK:318); word 7 is tmax and replaces the 9999 the running nearest hit starts from (RK:172).  Box pruning stays the
+ *     reference's (`d1 > nearest`, `d2 < nearest`).  (0.001, 9999) gives exactly rt_trace_rays.
+ *   - A NaN limit, or tmin >= tmax: a miss (the strict inequalities).
+ *   - A negative tmin is allowed: triangles behind the origin can then be hit.  Spheres still use only the near root (HK:317).
+ *   - A tmax of 99999 or more is honoured, but it disables the pruning of boxes the ray misses (hit_aabb's 99999, RK:405-407):
+ *     results stay correct, the walk gets slower.
+ *
+ * Occlusion.  occluded[i] = 1 if and only if rt_trace_rays_ex with the same flags reports a hit for ray i.  The walk stops at the
+ * first accepted triangle or sphere; until then it takes the limited nearest search's steps under the same bound, so both accept
+ * their first primitive at the same step or not at all. */
+int rt_trace_rays_ex(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, rt_hit* hits, void* hip_stream);  /* device, async */
+int rt_trace_rays_host_ex(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, rt_hit* hits);               /* host, sync   */
+int rt_occluded(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, uint8_t* occluded, void* hip_stream);  /* device, async */
+int rt_occluded_host(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, uint8_t* occluded);               /* host, sync   */
 
 /* ---- multi-GPU: render + RCCL gather behind one call (RR:434-470 across a group of GPUs) ------ */
 

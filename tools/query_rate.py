@@ -1,11 +1,14 @@
-"""Dev tool: the rate of ray queries (rt_trace_rays) beside the per-ray cost of an awaited frame of the reference's scene.
+"""Dev tool: the rate of ray queries -- nearest (rt_trace_rays), limited nearest (rt_trace_rays_ex with RT_QUERY_LIMITS) and
+occlusion (rt_occluded) -- beside the per-ray cost of an awaited frame of the reference's scene.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o q -- python tools/query_rate.py
 
 Workloads: the 1344x846 primary rays of the reference's scene (tests/golden/ref_scene.npz), 2^20 random rays on it (origins in
 the scene box, within 20 of the camera, grown by half, directions of random length), 2^20 random rays on C3 (1024 spheres).  Each
-runs REPS times through the device path on one stream; the kernel statistics of rocprofv3 (query_triangles / query_spheres) give
-the rays per ms of the query kernels, and the line printed here gives the same from hipEvents around the batch.  The frame's
+runs REPS times through the device path on one stream, once per kind: "nearest" (flags 0), "limited" (words 3 and 7 = 0.001 and
+9999, the same answers through the limited kernels) and "occluded" (the same limits); the kernel statistics of rocprofv3
+(query_triangles / query_spheres, limited_triangles / limited_spheres / occlude_spheres) give the rays per ms of the query
+kernels, and the line printed here gives the same from hipEvents around the batch.  The frame's
 figure is rt_stats.rays / kernel_ms of an awaited frame (RK:114 + RK:153 traversals, reflections and shadow rays included)."""
 import json
 import os
@@ -24,6 +27,7 @@ REPS = 20
 def ray_tensor(torch, o, d):
     rays = np.zeros((o.shape[0], 8), np.float32)
     rays[:, 0:3], rays[:, 4:7] = o, d
+    rays[:, 3], rays[:, 7] = 0.001, 9999.0            # the reference's limits: every kind answers the same rays the same way
     return torch.from_numpy(rays).to("cuda:0")
 
 
@@ -47,19 +51,31 @@ def random_rays(lo, hi, n, seed):
     return o, d.astype(np.float32)
 
 
-def timed(torch, r, rays):
-    out = torch.empty_like(rays)
-    r.trace_rays(rays, out=out)                   # warm-up (first-use work: corner array, code objects)
+def timed_one(torch, r, rays, kind):
+    if kind == "occluded":
+        out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
+        run = lambda: r.occluded(rays, out=out)
+    else:
+        out = torch.empty_like(rays)
+        run = lambda: r.trace_rays(rays, out=out, limits=kind == "limited")
+    run()                                         # warm-up (first-use work: corner array, code objects)
     torch.cuda.synchronize()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     for _ in range(REPS):
-        r.trace_rays(rays, out=out)
+        run()
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / REPS
-    hits = int((out[:, 3].view(torch.int32) >= 0).sum().item())
-    return {"rays": int(rays.shape[0]), "ms": round(ms, 4), "rays_per_ms": round(rays.shape[0] / ms), "hit_fraction": round(hits / rays.shape[0], 3)}
+    hits = int((out > 0).sum().item()) if kind == "occluded" else int((out[:, 3].view(torch.int32) >= 0).sum().item())
+    return {"ms": round(ms, 4), "rays_per_ms": round(rays.shape[0] / ms), "hit_fraction": round(hits / rays.shape[0], 3)}
+
+
+def timed(torch, r, rays):
+    res = {"rays": int(rays.shape[0])}
+    for kind in ("nearest", "limited", "occluded"):
+        res[kind] = timed_one(torch, r, rays, kind)
+    return res
 
 
 def main():
