@@ -1379,6 +1379,23 @@ int rt_order_tiles(rt_ctx* c, const uint32_t* cost, uint32_t n, uint32_t wave_sl
     return RT_OK;
 }
 
+int rt_read_hierarchy(rt_ctx* c, float* rec4, uint32_t* link, uint32_t cap_nodes, uint32_t* n_nodes) {
+    if (!c || !n_nodes) return fail(RT_ERR_INVALID_ARG, "rt_read_hierarchy: NULL argument");
+    *n_nodes = 0;
+    if (c->scene_kind != 0 || c->bvh_nodes == 0u || !c->d_bvh_rec || !c->d_bvh_link)
+        return fail(RT_ERR_STATE, "rt_read_hierarchy: no frame of this sphere scene has walked a hierarchy");
+    const uint32_t nodes = c->bvh_nodes;
+    *n_nodes = nodes;
+    if (cap_nodes < nodes + 1u || !rec4 || !link) return fail(RT_ERR_CAPACITY, "rt_read_hierarchy: need n_nodes + 1 entries");
+    RT_HIP(hipSetDevice(c->device));
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    const size_t nn = (size_t)nodes + 1u;
+    RT_HIP(hipMemcpyAsync(rec4, c->d_bvh_rec, nn * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(hipMemcpyAsync(link, c->d_bvh_link, nn * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
 int rt_filter_plan(const float* records, uint32_t n, const float params[24], int* filter_ok, int* signed_filter) {
     if ((n && !records) || !params || !filter_ok || !signed_filter) return fail(RT_ERR_INVALID_ARG, "rt_filter_plan: NULL argument");
     bool ok = false;

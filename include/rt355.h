@@ -410,6 +410,14 @@ int rt_build_flow(const float* nodes, uint32_t n_nodes, const uint32_t* roots, u
  * >= 4096 tiles. */
 int rt_order_tiles(rt_ctx* ctx, const uint32_t* cost, uint32_t n, uint32_t wave_slots, uint32_t* order, size_t cap);
 
+/* The bounding-sphere hierarchy on the device, as the latest frame that walked one left it: inner node records
+ * after the refit of moved spheres (rt_bvh.hip: bvh_refit) or as the host built them, leaf records as the
+ * device filled them (the filter records of the spheres), the links and the sentinel -- the layout of
+ * rt_build_hierarchy.  Waits for the frames in flight first; changes nothing a later frame renders.
+ * RT_ERR_STATE when the context holds no hierarchy (a triangle scene, or no frame has walked one yet);
+ * RT_ERR_CAPACITY when cap_nodes < n_nodes + 1 (*n_nodes is set either way). */
+int rt_read_hierarchy(rt_ctx* ctx, float* rec4, uint32_t* link, uint32_t cap_nodes, uint32_t* n_nodes);
+
 /* Which filter forms a frame of this scene may use (no device needed): *filter_ok = 0 when
  * max(|center| + |radius| over the spheres, |cameraPos|, |lightPosition|) is NaN, infinite or
  * >= 2^20 -- fast mode then renders the frame with the literal kernel --, *signed_filter = 1 when

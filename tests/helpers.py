@@ -386,9 +386,11 @@ class SphereForm:
         return "SphereForm(%d, %s, sgn=%s, flat=%s, cap=%s, resolve=%s)" % (self.kernel_id, self.form, self.sgn, self.flat, self.cap, self.resolve)
 
 
-def expected_sphere_form(scene, bounces, strict=False, variant=0, sky=None, in_flight=False):
+def expected_sphere_form(scene, bounces, strict=False, variant=0, sky=None, in_flight=False, nodes=None):
     """The form rt_enqueue / rt_launch_trace / rt_launch_bvh must give a sphere frame.  in_flight: the library has seen the
-    previous batch of frames in flight on its own streams (rt_wait: pipelined_hint).  None: the frame is refused."""
+    previous batch of frames in flight on its own streams (rt_wait: pipelined_hint).  nodes: the node count of the hierarchy
+    on the device (rt_read_hierarchy), which after a refit or a handoff need not be that of a fresh build of the scene;
+    None: a fresh build's.  None: the frame is refused."""
     sky = sky if sky is not None else rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA)
     flat = sky_is_flat(sky)
     n = len(scene.spheres)
@@ -399,7 +401,7 @@ def expected_sphere_form(scene, bounces, strict=False, variant=0, sky=None, in_f
     use_bvh = fast and filter_ok and n > 0 and (variant == 4 or (variant == 0 and n >= (72 if in_flight else 128)))
     queue = not use_bvh and fast and filter_ok and (variant in (2, 3) or (variant in (0, 4, 5) and n >= 320))
     if use_bvh:                                                            # rt_bvh.hip launch_bvh
-        nodes = hierarchy_nodes(scene)
+        nodes = hierarchy_nodes(scene) if nodes is None else nodes
         resolve = not flat                                                 # rt_launch_sky_resolve behind a textured sky
         for kid, waves, cap, k in ((KID_HIERARCHY_8, 8, 12, 3), (KID_HIERARCHY_12, 12, 12, 2), (KID_HIERARCHY_12, 12, 6, 2)):
             if lds_fits(k, bvh_room(nodes, waves, cap)):
@@ -545,3 +547,190 @@ def crowded_case(n, sgn, sky):
     scene = rt.SceneRaytracing().createScene(crowded_spheres(n, 5, unsigned=sgn == 0))
     s = (rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA) if sky == "flat" else random_sky(n) if sky == "cube" else non_cube_sky(n))
     return scene, s
+
+
+# ---- the sphere hierarchy's records restated (tests/test_hierarchy_cpu.py, test_refit_model_cpu.py, test_moving_spheres_gpu.py) ----
+LEAF = 0x80000000
+FILTER_SCALE = 2.0 ** 40                                                  # rt_filter.h: RT_FILTER_SCALE (its square: SCALE2)
+FILTER_EPS, FILTER_KAPPA = 2.0 ** -17, 2.0 ** -16                         # RT_FILTER_EPS, RT_FILTER_KAPPA
+BVH_SIGMA = 1.04                                                          # rt_bvh_build.h: RT_BVH_SIGMA
+
+
+def build_hierarchy(records):
+    """rt_build_hierarchy of (n, 8) float32 records: (rec4 (m+1, 4), link (m+1,), m), sentinel included."""
+    import ctypes
+    from compute_raytracer_amd import abi
+    rec = np.ascontiguousarray(records, np.float32).reshape(-1, 8)
+    n = rec.shape[0]
+    cap = 2 * n + 64
+    out, link, nodes = np.zeros((cap, 4), np.float32), np.zeros(cap, np.uint32), ctypes.c_uint32(0)
+    fp = ctypes.POINTER(ctypes.c_float)
+    abi.check(abi.load().rt_build_hierarchy(rec.ctypes.data_as(fp), n, out.ctypes.data_as(fp),
+                                            link.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), cap, ctypes.byref(nodes)))
+    m = nodes.value
+    return out[: m + 1].copy(), link[: m + 1].copy(), m
+
+
+def _members_f64(records):
+    """centres and |radius| in f64 with NaN taken as 0 (rt_bvh_build.h cx / rad, rt_bvh.hip bvh_refit: sphere)"""
+    rec = np.asarray(records, np.float32).reshape(-1, 8)
+    c = rec[:, 0:3].astype(np.float64)
+    r = np.abs(rec[:, 7].astype(np.float64))
+    c[np.isnan(c)] = 0.0
+    r[np.isnan(r)] = 0.0
+    return c, r
+
+
+def leaf_records(records):
+    """The filter record of each sphere, as rt_kernels.hip prep_spheres writes geo_f (and bvh_fill_leaves copies it into the
+    hierarchy's leaves): centre * 2^40 in f32, k = fl32((|c|^2 (1-eps) - fl32(r*r) (1+kappa)) * 2^80) with |c|^2 in f64."""
+    rec = np.asarray(records, np.float32).reshape(-1, 8)
+    c = rec[:, 0:3]
+    r2 = rec[:, 7] * rec[:, 7]                                            # f32 product (HK:310 radius * radius)
+    cd = c.astype(np.float64)
+    cd2 = cd[:, 0] * cd[:, 0] + cd[:, 1] * cd[:, 1] + cd[:, 2] * cd[:, 2]
+    k = cd2 * (1.0 - FILTER_EPS) - r2.astype(np.float64) * (1.0 + FILTER_KAPPA)
+    out = np.empty((rec.shape[0], 4), np.float32)
+    out[:, 0:3] = c * np.float32(FILTER_SCALE)
+    out[:, 3] = (k * FILTER_SCALE ** 2).astype(np.float32)
+    return out
+
+
+def refit_model(rec4, link, records):
+    """rt_bvh.hip bvh_refit, restated operation by operation in f64, for the topology `link` (rt_build_hierarchy's layout)
+    over `records`: every inner node's bound from its members (the leaves between it and its skip link) -- the centre of
+    their box, then up to 32 greedy steps of 0.05 R towards the farthest member while the radius falls, the centre rounded to
+    f32, the radius about that point times 1.04, k = |C|^2 (1-eps) - R^2 (1+kappa) in f64 rounded once to f32.  The
+    farthest member is the kernel's: member j sits on lane (j - first) % 64 (first = node + 1), each lane keeps the first
+    strict maximum of its stride, the lowest lane holding the wave's maximum speaks.  Leaves are the filter records
+    (leaf_records: bvh_fill_leaves), the sentinel is kept from rec4.  All nodes are refitted at once, one segment per node."""
+    rec4 = np.asarray(rec4, np.float32)
+    link = np.asarray(link, np.uint32)
+    m = link.shape[0] - 1
+    out = rec4.copy()
+    is_leaf = (link[:m] & LEAF) != 0
+    sph = (link[:m] & 0x7FFFFFFF).astype(np.int64)
+    out[:m][is_leaf] = leaf_records(records)[sph[is_leaf]]
+    inner = np.nonzero(~is_leaf)[0]
+    if inner.size == 0:
+        return out
+    c, r = _members_f64(records)
+    leaf_at = np.nonzero(is_leaf)[0]
+    segs = [leaf_at[np.searchsorted(leaf_at, i + 1): np.searchsorted(leaf_at, int(link[i]) >> 2)] for i in inner]
+    counts = np.array([len(g) for g in segs])
+    assert (counts >= 1).all(), "an inner node without members"
+    j = np.concatenate(segs)                                              # member node indices, node by node
+    seg = np.repeat(np.arange(inner.size), counts)                        # segment (inner node) of each member
+    starts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    jrel = j - (inner[seg] + 1)
+    key = (jrel % 64) * (1 << 32) + jrel                                  # (lane, position in the lane's stride)
+    cm, rm = c[sph[j]], r[sph[j]]
+
+    def radius_at(P):
+        dx = cm - P[seg]
+        d = np.sqrt(dx[:, 0] * dx[:, 0] + dx[:, 1] * dx[:, 1] + dx[:, 2] * dx[:, 2]) + rm
+        R = np.maximum.reduceat(d, starts)
+        kmin = np.minimum.reduceat(np.where(d == R[seg], key, np.iinfo(np.int64).max), starts)
+        far = c[sph[inner + 1 + (kmin & 0xFFFFFFFF)]]
+        return R, far
+
+    mn = np.minimum.reduceat(cm - rm[:, None], starts, axis=0)
+    mx = np.maximum.reduceat(cm + rm[:, None], starts, axis=0)
+    P = 0.5 * (mn + mx)
+    Rp, far = radius_at(P)
+    active = np.ones(inner.size, bool)
+    for _ in range(32):
+        s = far - P
+        ln = np.sqrt(s[:, 0] * s[:, 0] + s[:, 1] * s[:, 1] + s[:, 2] * s[:, 2])
+        active &= ln > 1e-12
+        if not active.any():
+            break
+        Q = P + s / np.where(active, ln, 1.0)[:, None] * 0.05 * Rp[:, None]
+        Rq, farq = radius_at(Q)
+        active &= Rq < Rp
+        P = np.where(active[:, None], Q, P)
+        Rp = np.where(active, Rq, Rp)
+        far = np.where(active[:, None], farq, far)
+    C = P.astype(np.float32)
+    Cd = C.astype(np.float64)
+    R = radius_at(Cd)[0] * BVH_SIGMA
+    c2 = Cd[:, 0] * Cd[:, 0] + Cd[:, 1] * Cd[:, 1] + Cd[:, 2] * Cd[:, 2]
+    k = c2 * (1.0 - FILTER_EPS) - R * R * (1.0 + FILTER_KAPPA)
+    out[inner, 0:3] = C * np.float32(FILTER_SCALE)
+    out[inner, 3] = (k * FILTER_SCALE ** 2).astype(np.float32)
+    return out
+
+
+def check_tree(rec, out, link, m, tight=True):
+    """The invariants the device walk relies on, for n (n, 8) records and a hierarchy (out (m+1, 4), link (m+1,)) in
+    rt_build_hierarchy's layout: depth-first layout with forward skip links and a self-linked sentinel, every sphere a leaf
+    exactly once, every inner node containing its members with the 4 % slack of the proof (rt_bvh.hip, header).
+    tight: the host build's records -- leaves zero (the device fills them), radii within 5 % of the members' bound.  False:
+    records refitted on the device (bvh_refit) or by refit_model, whose centre comes from the greedy walk alone and whose
+    leaves hold the filter records (compared with leaf_records elsewhere): the slack bound only."""
+    rec = np.asarray(rec, np.float32).reshape(-1, 8)
+    n = rec.shape[0]
+    S = FILTER_SCALE
+    assert n <= m <= 2 * n + 64
+    assert link[m] == 4 * m and np.isinf(out[m, 3]) and out[m, 3] > 0          # sentinel
+    leaves = link[:m][(link[:m] & LEAF) != 0] & 0x7FFFFFFF
+    assert sorted(leaves.tolist()) == list(range(n))                            # every sphere exactly once
+    c, r = _members_f64(rec)
+    for i in range(m):
+        if link[i] & LEAF:
+            if tight:
+                assert not out[i].any()                                         # filled on the device
+            continue
+        assert link[i] % 4 == 0
+        end = link[i] // 4
+        assert i + 1 < end <= m                                                 # forward link, non-empty subtree
+        inner = [j for j in range(i + 1, end) if not (link[j] & LEAF)]
+        assert all(link[j] // 4 <= end for j in inner)                          # nested subtrees
+        members = link[i + 1 : end][(link[i + 1 : end] & LEAF) != 0] & 0x7FFFFFFF
+        assert len(members) >= 2
+        C = out[i, 0:3].astype(np.float64) / S
+        k = float(out[i, 3]) / (S * S)
+        c2 = float(C @ C)
+        need = (np.linalg.norm(c[members] - C, axis=1) + r[members]).max()
+        # k = |C|^2 (1-eps) - R^2 (1+kappa) with R >= 1.04 * need, stored in fp32 (the eps term of the
+        # node test covers that rounding, 2^-24 |k|, many times over)
+        round_k = 2.0 ** -23 * max(c2, need * need)
+        k_slack = c2 * (1.0 - FILTER_EPS) - (1.04 * need) ** 2 * (1.0 + FILTER_KAPPA)
+        assert k <= k_slack + round_k, (i, k, k_slack)          # the radius carries the 4 % slack of the proof
+        if tight:
+            k_tight = c2 * (1.0 - FILTER_EPS) - (1.05 * need) ** 2 * (1.0 + FILTER_KAPPA)
+            assert k >= k_tight - round_k - 1e-12, (i, k, k_tight)  # and not much more
+
+
+def drift_spheres(base, step, seed, keep=(0,)):
+    """(n, 8) records moved by `step`: every sphere but those in `keep` (a ground sphere, a tiny one: what puts the scene in
+    its filter class) drifts and breathes, and n // 50 of them, chosen by `seed`, jump across the scene's box."""
+    s = np.array(base, np.float32).reshape(-1, 8).copy()
+    n = s.shape[0]
+    mv = np.setdiff1d(np.arange(n), np.asarray(keep, np.int64))
+    s[mv, 0] += (0.35 * step * np.sin(mv * 0.37)).astype(np.float32)
+    s[mv, 1] += (0.20 * step * np.abs(np.cos(mv * 0.11))).astype(np.float32)
+    s[mv, 2] += (0.30 * step * np.cos(mv * 0.23)).astype(np.float32)
+    s[mv, 7] *= (1.0 + 0.04 * step * np.sin(mv * 0.5)).astype(np.float32)
+    rng = np.random.default_rng(seed)
+    jump = rng.choice(mv, size=max(1, n // 50), replace=False)
+    s[jump, 0] = rng.uniform(-12, 12, len(jump)).astype(np.float32)
+    s[jump, 2] = rng.uniform(-26, -3, len(jump)).astype(np.float32)
+    return s
+
+
+def teleport_spheres(base, seed, keep=(0,)):
+    """every sphere but those in `keep` somewhere else in the scene's box: a topology built for `base` groups them at random"""
+    s = np.array(base, np.float32).reshape(-1, 8).copy()
+    mv = np.setdiff1d(np.arange(s.shape[0]), np.asarray(keep, np.int64))
+    rng = np.random.default_rng(seed)
+    s[mv, 0] = rng.uniform(-12, 12, len(mv)).astype(np.float32)
+    s[mv, 1] = rng.uniform(0.05, 3, len(mv)).astype(np.float32)
+    s[mv, 2] = rng.uniform(-26, -3, len(mv)).astype(np.float32)
+    return s
+
+
+# Motions (drift_spheres seed, step) of two SPHERE_CASES cells whose fresh build lands on the other side of the cell's LDS edge,
+# and the form (and list capacity) it lands in (tests/test_refit_model_cpu.py checks them, test_moving_spheres_gpu.py hands
+# such a topology over)
+MOVING_BOUNDARY_MOTIONS = {"bvh8-cap12-sgn1-flat": (0, 2, ("bvh12", 12)), "bvh16-cap6-sgn1-flat": (0, 3, ("bvh_global", 8))}

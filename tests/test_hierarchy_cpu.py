@@ -12,9 +12,7 @@ import compute_raytracer_amd as rt
 from compute_raytracer_amd import abi
 from compute_raytracer_amd.scene_raytracing import synthetic_spheres
 
-LEAF = 0x80000000
-S = 2.0 ** 40
-EPS, KAPPA = 2.0 ** -17, 2.0 ** -16
+from helpers import LEAF, check_tree
 
 
 def build(spheres):
@@ -31,37 +29,6 @@ def build(spheres):
     m = nodes.value
     return rec, out[: m + 1].copy(), link[: m + 1].copy(), m
 
-
-def check_tree(rec, out, link, m):
-    n = rec.shape[0]
-    assert n <= m <= 2 * n + 64
-    assert link[m] == 4 * m and np.isinf(out[m, 3]) and out[m, 3] > 0          # sentinel
-    leaves = link[:m][(link[:m] & LEAF) != 0] & 0x7FFFFFFF
-    assert sorted(leaves.tolist()) == list(range(n))                            # every sphere exactly once
-    c = rec[:, 0:3].astype(np.float64)
-    r = np.abs(rec[:, 7].astype(np.float64))
-    for i in range(m):
-        if link[i] & LEAF:
-            assert not out[i].any()                                             # filled on the device
-            continue
-        assert link[i] % 4 == 0
-        end = link[i] // 4
-        assert i + 1 < end <= m                                                 # forward link, non-empty subtree
-        inner = [j for j in range(i + 1, end) if not (link[j] & LEAF)]
-        assert all(link[j] // 4 <= end for j in inner)                          # nested subtrees
-        members = link[i + 1 : end][(link[i + 1 : end] & LEAF) != 0] & 0x7FFFFFFF
-        assert len(members) >= 2
-        C = out[i, 0:3].astype(np.float64) / S
-        k = float(out[i, 3]) / (S * S)
-        c2 = float(C @ C)
-        need = (np.linalg.norm(c[members] - C, axis=1) + r[members]).max()
-        # k = |C|^2 (1-eps) - R^2 (1+kappa) with R >= 1.04 * need, stored in fp32 (the eps term of the
-        # node test covers that rounding, 2^-24 |k|, many times over)
-        round_k = 2.0 ** -23 * max(c2, need * need)
-        k_slack = c2 * (1.0 - EPS) - (1.04 * need) ** 2 * (1.0 + KAPPA)
-        k_tight = c2 * (1.0 - EPS) - (1.05 * need) ** 2 * (1.0 + KAPPA)
-        assert k <= k_slack + round_k, (i, k, k_slack)          # the radius carries the 4 % slack of the proof
-        assert k >= k_tight - round_k - 1e-12, (i, k, k_tight)  # and not much more
 
 @pytest.mark.parametrize("n,seed", [(2, 1), (5, 2), (9, 3), (64, 357), (1024, 358), (4096, 360)])
 def test_baseline_like_scenes(n, seed):

@@ -4,7 +4,14 @@ build in the frame's path, and must never cost a bit.
 
 After a sphere write with an unchanged count the library keeps the hierarchy's topology, refits the node
 bounds on the device (rt_bvh.hip: bvh_refit) and rebuilds the topology on a worker thread, taking it
-over at a later frame (rt_api.hip: rt_rebuild).  Every frame here is compared with the oracle."""
+over at a later frame (rt_api.hip: rt_rebuild).  Every frame here is compared with the oracle.
+
+The hierarchy the device walked is read back after every frame of the tests below the first two (rt_read_hierarchy) and
+checked three ways: its links are the topology rt_build_hierarchy gives one of the record sets written so far (the build is
+deterministic), its inner records are helpers.refit_model of those links over the frame's records bit for bit (the host
+build's own records on the first frame after a count change) and keep the walk's slack (check_tree(tight=False)), its
+leaves are the spheres' filter records and its sentinel is {0, 0, 0, +inf} linked to itself.  The frame's form must be the
+one launch_bvh gives the DEVICE's node count, which a handoff can move across an LDS edge in mid-animation."""
 import ctypes
 import time
 
@@ -13,18 +20,23 @@ import pytest
 
 import compute_raytracer_amd as rt
 from compute_raytracer_amd import abi
-from compute_raytracer_amd.scene_raytracing import CONSTANT_SKY_RGBA
+from compute_raytracer_amd.scene_raytracing import CONSTANT_SKY_RGBA, synthetic_spheres
+from helpers import (KID_BRUTE_SINGLE, KID_HIERARCHY_8, KID_HIERARCHY_GLOBAL, KID_LITERAL, LEAF, MOVING_BOUNDARY_MOTIONS,
+                     SPHERE_CASES, build_hierarchy, check_tree, drift_spheres, expected_sphere_form, leaf_records,
+                     refit_model, teleport_spheres, unsigned_ground_spheres)
 
 pytestmark = pytest.mark.gpu
 FP = ctypes.POINTER(ctypes.c_float)
 
 
 class Ctx:
-    def __init__(self, W, H, sky):
+    def __init__(self, W, H, sky, rank=0, world=1):
         self.L = abi.load()
         self.c = ctypes.c_void_p()
         abi.check(self.L.rt_create(0, ctypes.byref(self.c)))
         self.W, self.H = W, H
+        self.rows = [y for y in range(H) if (y // 8) % world == rank]
+        abi.check(self.L.rt_set_partition(self.c, rank, world), self.c)
         abi.check(self.L.rt_resize(self.c, W, H), self.c)
         for f in range(6):
             face = np.ascontiguousarray(sky.faces[f])
@@ -39,11 +51,30 @@ class Ctx:
 
     def frame(self):
         abi.check(self.L.rt_render(self.c), self.c)
-        img = np.zeros((self.H, self.W, 4), np.uint8)
+        img = np.zeros((len(self.rows), self.W, 4), np.uint8)
         abi.check(self.L.rt_read_pixels(self.c, img.ctypes.data, img.nbytes), self.c)
+        return img, self.stats().rays
+
+    def stats(self):
         st = abi.RtStats()
         abi.check(self.L.rt_get_stats(self.c, ctypes.byref(st)), self.c)
-        return img, st.rays
+        return st
+
+    def hierarchy(self):
+        """rt_read_hierarchy: (rec4 (m+1, 4), link (m+1,), m); None while the context holds none (RT_ERR_STATE)"""
+        m = ctypes.c_uint32(0)
+        u32p = ctypes.POINTER(ctypes.c_uint32)
+        rc = self.L.rt_read_hierarchy(self.c, None, None, 0, ctypes.byref(m))
+        if rc == abi.RT_ERR_STATE:
+            return None
+        assert rc == abi.RT_ERR_CAPACITY and m.value > 0, rc
+        n = m.value
+        rec4, link = np.zeros((n + 1, 4), np.float32), np.zeros(n + 1, np.uint32)
+        rc = self.L.rt_read_hierarchy(self.c, rec4.ctypes.data_as(FP), link.ctypes.data_as(u32p), n, ctypes.byref(m))
+        assert rc == abi.RT_ERR_CAPACITY and m.value == n                   # n_nodes + 1 entries are needed
+        abi.check(self.L.rt_read_hierarchy(self.c, rec4.ctypes.data_as(FP), link.ctypes.data_as(u32p), n + 1, ctypes.byref(m)), self.c)
+        assert m.value == n
+        return rec4, link, n
 
     def close(self):
         self.L.rt_destroy(self.c)
@@ -134,3 +165,346 @@ def test_frame_after_a_sphere_write_costs_about_a_static_frame():
         assert ratio < 1.3, ratio
     finally:
         c.close()
+
+
+# ---- the device's hierarchy, read back after every frame ----------------------------------------------------------------
+HIERARCHY_KIDS = range(KID_HIERARCHY_8, KID_HIERARCHY_GLOBAL + 1)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+class Records:
+    """a scene's camera and light with other sphere records: what expected_sphere_form reads of a scene"""
+    def __init__(self, scene, records):
+        self.scene, self.records = scene, records
+        self.spheres = range(records.shape[0])
+
+    def pack_spheres(self):
+        return self.records
+
+    def pack_params(self, bounces):
+        return self.scene.pack_params(bounces)
+
+
+class Moving:
+    """One context animating sphere records: every frame against the oracle (pixels and rays), its form against the
+    dispatcher restated for the device's node count, and the hierarchy read back against the topologies of the record sets
+    written so far, refit_model, the walk's slack and the filter records."""
+    def __init__(self, oracle, scene, sky, W, H, B, rank=0, world=1):
+        self.oracle, self.scene, self.sky, self.W, self.H, self.B = oracle, scene, sky, W, H, B
+        self.rank, self.world = rank, world
+        self.ctx = Ctx(W, H, sky, rank, world)
+        self.ctx.params(scene.pack_params(B))
+        self.written = []               # every record set written, in order
+        self._builds, self._refs = {}, {}
+        self.walked = None              # records of the latest frame that walked the hierarchy
+        self.topo_n = None              # sphere count of the device's topology
+        self.link = None                # links the device holds
+        self.m = None
+        self.frames, self.handoffs, self.kids = 0, 0, []
+        self.t_oracle = self.t_gpu = 0.0        # host seconds in the oracle, and in rt_render + read-back (printed)
+
+    def build(self, s):
+        key = s.tobytes()
+        if key not in self._builds:
+            self._builds[key] = build_hierarchy(s)
+        return self._builds[key]
+
+    def ref(self, s, p=None):
+        p = self.scene.pack_params(self.B) if p is None else p
+        key = (s.tobytes(), p.tobytes())
+        if key not in self._refs:
+            t0 = time.perf_counter()
+            self._refs[key] = self.oracle.render(p, s, self.sky.faces, self.W, self.H, tile_first=self.rank, tile_step=self.world)
+            self.t_oracle += time.perf_counter() - t0
+        return self._refs[key]
+
+    def write(self, s):
+        s = np.ascontiguousarray(s, np.float32).reshape(-1, 8)
+        self.ctx.spheres(s)
+        self.written.append(s)
+        self.cur = s
+
+    def frame(self, in_flight=False):
+        t0 = time.perf_counter()
+        img, rays = self.ctx.frame()
+        self.t_gpu += time.perf_counter() - t0
+        ref, _, ref_rays = self.ref(self.cur)
+        self.frames += 1
+        assert np.array_equal(img, ref[self.ctx.rows]), ("frame", self.frames, int((img != ref[self.ctx.rows]).any(-1).sum()))
+        assert rays == ref_rays, ("rays", self.frames)
+        return self.after(self.ctx.stats().kernel_id, in_flight)
+
+    def after(self, kid, in_flight=False):
+        """the checks of the hierarchy and of the form, once the frames enqueued so far have rendered the current records"""
+        self.kids.append(kid)
+        if kid in HIERARCHY_KIDS:
+            host_build = self.topo_n != self.cur.shape[0]
+            self.walked, self.topo_n = self.cur, self.cur.shape[0]
+        got = self.ctx.hierarchy()
+        if self.walked is None:
+            assert got is None, "rt_read_hierarchy before any frame walked a hierarchy"
+            nodes = None
+        else:
+            rec4, link, m = got
+            self.check(rec4, link, m, host_build if kid in HIERARCHY_KIDS else None)
+            nodes = m
+        want = expected_sphere_form(Records(self.scene, self.cur), self.B, sky=self.sky, in_flight=in_flight, nodes=nodes)
+        assert want is not None and kid == want.kernel_id, ("form", self.frames, kid, want)
+        return kid
+
+    def check(self, rec4, link, m, host_build):
+        s = self.walked
+        if host_build is None:                      # a frame of another kernel: the hierarchy stays as the last walk left it
+            assert m == self.m and np.array_equal(link, self.link) and np.array_equal(bits(rec4), bits(self.rec4))
+            return
+        same = [k for k, w in enumerate(self.written) if w.shape == s.shape and self.build(w)[2] == m
+                and np.array_equal(self.build(w)[1], link)]
+        assert same, ("the device's links are the topology of no record set written so far", self.frames)
+        if self.link is not None and (self.m != m or not np.array_equal(self.link, link)):
+            self.handoffs += 0 if host_build else 1
+        assert link[m] == 4 * m and np.array_equal(bits(rec4[m]), bits(np.float32([0, 0, 0, np.inf])))      # sentinel
+        leaf = (link[:m] & LEAF) != 0
+        assert np.array_equal(bits(rec4[:m][leaf]), bits(leaf_records(s)[link[:m][leaf] & 0x7FFFFFFF])), "leaf records"
+        inner = ~leaf
+        want = self.build(s)[0] if host_build else refit_model(rec4, link, s)
+        bad = np.nonzero((bits(rec4[:m][inner]) != bits(want[:m][inner])).any(-1))[0]
+        assert bad.size == 0, ("inner records differ from the %s" % ("host build" if host_build else "refit model"),
+                               self.frames, int(bad.size), int(np.nonzero(inner)[0][bad[0]]))
+        check_tree(s, rec4, link, m, tight=False)
+        self.rec4, self.link, self.m = rec4, link, m
+
+    def force_handoff(self, A, within=2.0):
+        """Writes A and renders; then rewrites A and renders until the device walks the topology the worker built for A
+        (or for the rewrite of A: the same), within `within` seconds of host time.  Returns the frames it took."""
+        target = self.build(np.ascontiguousarray(A, np.float32))
+        assert not (target[2] == self.m and np.array_equal(target[1], self.link)), "A's topology is the device's already"
+        self.write(A)
+        self.frame()
+        t0, frames = time.monotonic(), 1
+        while not (self.m == target[2] and np.array_equal(self.link, target[1])):
+            assert time.monotonic() - t0 < within, "no handoff of the worker's topology within %.1f s (%d frames)" % (within, frames)
+            time.sleep(0.02)
+            self.write(A)
+            self.frame()
+            frames += 1
+        return frames
+
+    def report(self, what):
+        print("%s: %d frames, %d handoffs, forms %s, oracle %.2f s, GPU %.3f s"
+              % (what, self.frames, self.handoffs, self.kids, self.t_oracle, self.t_gpu))
+
+    def close(self):
+        self.ctx.close()
+
+
+def keep_of(case, n):
+    """the spheres that put a SPHERE_CASES scene in its filter class: the ground sphere, and the tiny one of the unsigned twin"""
+    return (0, n - 1) if case.sgn == 0 and case.unsigned == "tiny" else (0,)
+
+
+BVH_CELLS = [c.name for c in SPHERE_CASES if c.form.startswith("bvh") and
+             ((c.sgn == 1 and c.sky_kind == "flat") or (c.sgn == 0 and c.sky_kind != "flat"))]
+
+
+@pytest.mark.parametrize("name", BVH_CELLS)
+def test_every_hierarchy_form_moves_with_the_oracle(oracle, name):
+    """The six hierarchy rows of SPHERE_CASES (8, 12 and 16 waves, 12- and 6-entry lists, global nodes), each signed under a
+    flat sky and unsigned under a textured one (sky_resolve behind every frame): a static frame, two drift frames, a forced
+    handoff of the worker's topology, and a teleport the device's topology was not built for."""
+    case = next(c for c in SPHERE_CASES if c.name == name)
+    scene, sky = case.scene(), case.sky()
+    base = np.ascontiguousarray(scene.pack_spheres(), np.float32).reshape(-1, 8)
+    keep = keep_of(case, base.shape[0])
+    mv = Moving(oracle, scene, sky, case.W, case.H, case.B)
+    try:
+        mv.write(base)
+        mv.frame()
+        want = case.expected(scene=scene)
+        assert (want.form, want.cap, want.sgn) == (case.form, case.cap, case.sgn) and mv.kids[-1] == want.kernel_id
+        for step in (1, 2):
+            mv.write(drift_spheres(base, step, 31 * step, keep))
+            mv.frame()
+        mv.force_handoff(drift_spheres(base, 3, 97, keep))
+        mv.write(teleport_spheres(base, 5, keep))
+        mv.frame()
+        assert mv.handoffs >= 1
+        mv.report(name)
+    finally:
+        mv.close()
+
+
+@pytest.mark.parametrize("name", sorted(MOVING_BOUNDARY_MOTIONS))
+def test_handoff_switches_the_form(oracle, name):
+    """At the LDS edge of a form: the worker's topology for the recorded motion (tests/test_refit_model_cpu.py) has more
+    nodes than the device's buffer holds, so the frame that takes it over reallocates the node arrays and runs the next
+    form -- and still renders the oracle's frame; then the original records refitted on that topology."""
+    seed, step, other = MOVING_BOUNDARY_MOTIONS[name]
+    case = next(c for c in SPHERE_CASES if c.name == name)
+    scene, sky = case.scene(), case.sky()
+    base = np.ascontiguousarray(scene.pack_spheres(), np.float32).reshape(-1, 8)
+    mv = Moving(oracle, scene, sky, case.W, case.H, case.B)
+    try:
+        mv.write(base)
+        kid0 = mv.frame()
+        m0 = mv.m
+        A = drift_spheres(base, step, seed)
+        mv.force_handoff(A)
+        there = expected_sphere_form(Records(scene, A), case.B, sky=sky, nodes=mv.m)
+        assert mv.m > m0 and (there.form, there.cap) == other and mv.kids[-1] == there.kernel_id != kid0
+        mv.write(base)
+        mv.frame()
+        assert mv.kids[-1] == there.kernel_id
+        mv.report("%s: %d -> %d nodes" % (name, m0, mv.m))
+    finally:
+        mv.close()
+
+
+def test_filter_class_transitions_at_one_count(oracle):
+    """300 spheres, one count throughout: one sphere carries the reach across 342 (signed -> unsigned filter) and across 2^20
+    (the literal kernel: no refit, the hierarchy stays as it was), and back; a NaN goes into one record (literal again) and
+    out.  The first hierarchy frame after each literal stretch refits a topology the worker built meanwhile."""
+    W, H, B = 160, 96, 4
+    scene = rt.SceneRaytracing().createScene(synthetic_spheres(300, 41))
+    sky = rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA)
+    base = np.ascontiguousarray(scene.pack_spheres(), np.float32).reshape(-1, 8)
+    mv = Moving(oracle, scene, sky, W, H, B)
+    try:
+        mv.write(base)
+        mv.frame()
+        assert expected_sphere_form(scene, B).sgn == 1
+        s = drift_spheres(base, 1, 1)
+        s[7, 0:3] = [0.0, 1.0, -400.0]                           # reach ~401: the unsigned filter
+        mv.write(s)
+        assert mv.frame() in HIERARCHY_KIDS and expected_sphere_form(Records(scene, s), B).sgn == 0
+        for stretch in ("far", "nan"):
+            before = (mv.m, mv.link)
+            t = drift_spheres(base, 2, 2)
+            if stretch == "far":
+                t[7, 0:3] = [0.0, 1.0, -2.0e6]                   # reach beyond 2^20: literal
+            else:
+                t[200, 0] = np.nan                               # a NaN anywhere: literal
+            mv.write(t)
+            assert mv.frame() == KID_LITERAL
+            literal_sets = len(mv.written) - 1
+            time.sleep(0.2)                                      # the worker finishes the topology for t
+            mv.write(drift_spheres(base, 3, 3))
+            assert mv.frame() in HIERARCHY_KIDS
+            from_stretch = [w for w in mv.written[literal_sets:] if np.array_equal(mv.build(w)[1], mv.link)]
+            assert from_stretch, (stretch, "the first hierarchy frame after the literal stretch kept the old topology")
+            assert not (before[0] == mv.build(t)[2] and np.array_equal(before[1], mv.build(t)[1]))
+        mv.report("filter classes")
+    finally:
+        mv.close()
+
+
+def test_count_changes_and_back(oracle):
+    """n, n/2, n without waiting for the worker: its `ready` topology may still belong to an earlier n-sphere scene when
+    the count comes back.  Whichever topology the device takes, the tree keeps its bounds and the frame is the oracle's."""
+    W, H, B = 160, 96, 3
+    n = 640
+    scene = rt.SceneRaytracing().createScene(synthetic_spheres(n, 43))
+    sky = rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA)
+    base = np.ascontiguousarray(scene.pack_spheres(), np.float32).reshape(-1, 8)
+    mv = Moving(oracle, scene, sky, W, H, B)
+    try:
+        for s in (base, drift_spheres(base, 1, 1), base[: n // 2], base, drift_spheres(base, 2, 2), drift_spheres(base, 3, 3),
+                  drift_spheres(base, 1, 4)[: n // 2], drift_spheres(base[: n // 2], 2, 5), drift_spheres(base, 4, 6),
+                  drift_spheres(base, 5, 7)):
+            mv.write(s)
+            assert mv.frame() in HIERARCHY_KIDS
+        mv.report("count changes")
+    finally:
+        mv.close()
+
+
+def test_topology_survives_brute_force_frames_in_flight(oracle):
+    """100 spheres: awaited frames take the brute-force kernel, batches in flight the 8-wave hierarchy once the library has
+    seen a batch (pipelined_hint).  Spheres move between batches; brute-force frames leave the hierarchy as it was, and the
+    next hierarchy batch refits it (or a topology the worker built meanwhile).  Frames are read back while in flight
+    (rt_read_pixels_async)."""
+    W, H, B = 160, 96, 4
+    scene = rt.SceneRaytracing().createScene(synthetic_spheres(100, 7))
+    sky = rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA)
+    base = np.ascontiguousarray(scene.pack_spheres(), np.float32).reshape(-1, 8)
+    mv = Moving(oracle, scene, sky, W, H, B)
+    L, c = mv.ctx.L, mv.ctx.c
+    nbytes = H * W * 4
+    ptrs = []
+    for _ in range(4):
+        p = ctypes.c_void_p()
+        abi.check(L.rt_host_alloc(nbytes, ctypes.byref(p)))
+        ptrs.append(p)
+    host = [np.frombuffer((ctypes.c_uint8 * nbytes).from_address(p.value), np.uint8).reshape(H, W, 4) for p in ptrs]
+
+    def batch(hint):
+        refs, params = [], []
+        for f in range(4):
+            scene.camera.move(0.03, -0.02)
+            p = scene.pack_params(B)
+            params.append(p)
+            refs.append(mv.ref(mv.cur, p))
+        t0 = time.perf_counter()
+        for p in params:
+            mv.ctx.params(p)
+            abi.check(L.rt_render(c), c)
+        for f in range(4):
+            abi.check(L.rt_read_pixels_async(c, 3 - f, host[f].ctypes.data, nbytes), c)
+        abi.check(L.rt_wait(c), c)
+        abi.check(L.rt_read_pixels_wait(c), c)
+        mv.t_gpu += time.perf_counter() - t0
+        for f in range(4):
+            assert np.array_equal(host[f], refs[f][0]), ("batch frame", f)
+        mv.frames += 4
+        assert mv.ctx.stats().rays == refs[-1][2]
+        return mv.after(mv.ctx.stats().kernel_id, in_flight=hint)
+
+    try:
+        mv.write(base)
+        assert mv.frame() == KID_BRUTE_SINGLE and mv.walked is None          # no hierarchy yet: RT_ERR_STATE
+        assert batch(False) == KID_BRUTE_SINGLE                             # the first batch: no hint yet
+        for s in (drift_spheres(base, 1, 1), drift_spheres(base, 2, 2)):
+            mv.write(s)
+            assert batch(True) == KID_HIERARCHY_8                           # host build, then a refit
+        mv.write(drift_spheres(base, 3, 3))
+        assert mv.frame(in_flight=True) == KID_HIERARCHY_8                  # awaited, the hint still set: the hierarchy
+        mv.write(drift_spheres(base, 4, 4))
+        assert mv.frame() == KID_BRUTE_SINGLE                               # an awaited frame cleared the hint
+        mv.write(teleport_spheres(base, 5))
+        assert batch(False) == KID_BRUTE_SINGLE
+        time.sleep(0.05)
+        mv.write(drift_spheres(base, 5, 6))
+        assert batch(True) == KID_HIERARCHY_8                               # the topology of brute-force frames' records, refitted
+        mv.report("in flight")
+    finally:
+        mv.close()
+        for p in ptrs:
+            L.rt_host_free(p)
+
+
+@pytest.mark.parametrize("sgn", [1, 0])
+def test_moving_scene_as_rank_3_of_8(oracle, sgn):
+    """The 12-wave form with 6-entry lists as rank 3 of 8 (the small-share tail), spheres moving: static, two drifts, a forced
+    handoff, a teleport; each frame the oracle's rows of that rank."""
+    W, H, B, rank, world = 160, 192, 4, 3, 8
+    spheres = (synthetic_spheres if sgn else unsigned_ground_spheres)(2106, 7)
+    scene = rt.SceneRaytracing().createScene(spheres)
+    want = expected_sphere_form(scene, B)
+    assert (want.form, want.cap, want.sgn) == ("bvh12", 6, sgn)
+    base = np.ascontiguousarray(scene.pack_spheres(), np.float32).reshape(-1, 8)
+    sky = rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA)
+    mv = Moving(oracle, scene, sky, W, H, B, rank=rank, world=world)
+    try:
+        mv.write(base)
+        assert mv.frame() == want.kernel_id
+        for step in (1, 2):
+            mv.write(drift_spheres(base, step, 50 + step))
+            mv.frame()
+        mv.force_handoff(drift_spheres(base, 3, 53))
+        mv.write(teleport_spheres(base, 54))
+        mv.frame()
+        mv.report("rank 3 of 8, sgn %d" % sgn)
+    finally:
+        mv.close()
