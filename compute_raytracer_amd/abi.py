@@ -37,6 +37,7 @@ SYMBOLS = [
     "rt_read_pixels_async", "rt_read_pixels_wait", "rt_host_alloc", "rt_host_free",
     "rt_trace_rays", "rt_trace_rays_host", "rt_pick",
     "rt_trace_rays_ex", "rt_trace_rays_host_ex", "rt_occluded", "rt_occluded_host",
+    "rt_build_hierarchy_ex",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -141,6 +142,8 @@ def load():
         "rt_assemble_frame": (ctypes.c_int, [vp, vp, vp, u32, vp]),
         "rt_device_pixels": (ctypes.c_int, [vp, ctypes.POINTER(vp), ctypes.POINTER(sz)]),
         "rt_build_hierarchy": (ctypes.c_int, [fp, u32, fp, ctypes.POINTER(u32), u32, ctypes.POINTER(u32)]),
+        "rt_build_hierarchy_ex": (ctypes.c_int, [fp, u32, fp, ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32,
+                                                 ctypes.POINTER(ctypes.c_double)]),
         "rt_filter_plan": (ctypes.c_int, [fp, u32, fp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
         "rt_order_tiles": (ctypes.c_int, [vp, ctypes.POINTER(u32), u32, u32, ctypes.POINTER(u32), sz]),
         "rt_read_hierarchy": (ctypes.c_int, [vp, fp, ctypes.POINTER(u32), u32, ctypes.POINTER(u32)]),

@@ -1324,11 +1324,18 @@ int rt_assemble_frame(rt_ctx* c, const void* gathered, void* frame, uint32_t wor
 
 int rt_build_hierarchy(const float* records, uint32_t n, float* rec4, uint32_t* link, uint32_t cap_nodes,
                        uint32_t* n_nodes) {
+    return rt_build_hierarchy_ex(records, n, rec4, link, cap_nodes, n_nodes, RT355_HIERARCHY_PASSES, nullptr);
+}
+
+int rt_build_hierarchy_ex(const float* records, uint32_t n, float* rec4, uint32_t* link, uint32_t cap_nodes,
+                          uint32_t* n_nodes, uint32_t passes, double* info) {
     if ((n && !records) || !n_nodes) return fail(RT_ERR_INVALID_ARG, "rt_build_hierarchy: NULL argument");
     std::vector<float> r;
     std::vector<uint32_t> l;
-    const uint32_t nodes = rt_bvh_build(records, n, r, l, rt_bvh_arity());
+    rt_bvh_build_info bi;
+    const uint32_t nodes = rt_bvh_build(records, n, r, l, rt_bvh_arity(), passes > 16u ? 16u : passes, &bi);
     *n_nodes = nodes;
+    if (info) { info[0] = (double)bi.nodes_topdown; info[1] = (double)bi.moves; info[2] = bi.cost_topdown; info[3] = bi.cost; }
     if (l.empty()) return RT_OK;                       // n == 0: nothing to write
     if (cap_nodes < nodes + 1u || !rec4 || !link) return fail(RT_ERR_CAPACITY, "rt_build_hierarchy: need n_nodes + 1 entries");
     std::memcpy(rec4, r.data(), r.size() * sizeof(float));

@@ -391,6 +391,16 @@ int rt_group_wait(rt_group* g);
 int rt_build_hierarchy(const float* records, uint32_t n, float* rec4, uint32_t* link, uint32_t cap_nodes,
                        uint32_t* n_nodes);
 
+/* rt_build_hierarchy with the build's own figures.  The tree is built top-down and then optimised by `passes` rounds of
+ * reinsertion ("Structure"); rt_build_hierarchy and the renderer use RT355_HIERARCHY_PASSES, 0 gives the
+ * top-down tree as built.  info (may be NULL) receives four doubles: the node count of the top-down tree (the optimised
+ * tree has the same), the reinsertions kept, and the cost -- the sum over inner nodes of (radius of the members' bound)^2
+ * x children, which goes with the number of node tests a ray makes -- of the top-down tree and of the tree written (never
+ * higher). */
+#define RT355_HIERARCHY_PASSES 1u
+int rt_build_hierarchy_ex(const float* records, uint32_t n, float* rec4, uint32_t* link, uint32_t cap_nodes,
+                          uint32_t* n_nodes, uint32_t passes, double* info);
+
 /* Runs the HOST side of the triangle kernel's pair-record forms on its own (no device, no context): the relinked copy of the BLAS
  * trees they walk.  `nodes`: the node buffer as rt_write_nodes receives it (8 f32 per node); `roots`: the
  * rootNodeIndex of every instance.  Writes *n_pairs records of 16 words {c1.min.xyz, meta1, c1.max.xyz, 0, c2.min.xyz, meta2,
