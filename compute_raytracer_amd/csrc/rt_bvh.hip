@@ -88,6 +88,20 @@
 //        2 Rg + e1 + |T'_C|; 2 Rg * 1.69e-3 |T'_C| <= 1.69e-3 (15.4 Rg^2 + T'_C^2 / 15.4) = 0.026 Rg^2 + 1.1e-4 T'_C^2 (under
 //        2 kappa_h T'_C^2 = 1.22e-4 T'_C^2 less the 14u); 2 Rg * 1.69e-3 lam <= 0.045 Rg^2 + 6.3e-5 lam^2; the rest
 //        6.8e-3 Rg^2 + second-order terms < 0.003 Rg^2: 0.081 Rg^2 + 6.3e-5 lam^2 in all.  m >= 2.44e-4 lam^2 covers both.
+//   D. What need not be walked at all (shadow_decided below; every form, the unsigned ones too: the claim is about RK:147-165,
+//      not about the walk).  Let k be the sphere the reflection ray has just hit, and let the reference's literal test accept
+//      k on the shadow ray (L, s) at t_k (all of HK:316-318: disc > 0, t_k > 0.001, t_k < 9999).  The reference's loop tests k
+//      like every sphere, so its nearest hit has 0.001 < t_min <= t_k.  A mirrors: for any t <= l, |L + t s - P| >= (l - t) - 7ut,
+//      and forming the hit point, the difference and its length costs < u (2t + |L|) and a relative 4u, so a literal
+//      t <= l - dA, dA = 0.005001 + 10u (l + |L|), yields a computed diff >= (l - t - 9ut - u |L|) (1 - 4u) >= 0.005001 (1 - 4u) > 0.005: with
+//      t_k <= l - dA the hit at t_min is not at P whatever else is in the scene, and RK:165 returns minIntensity -- no
+//      traversal.  Nothing here assumes that P lies on k: P = fl(ro + t rd) may be off the surface by far more than an ulp
+//      after a grazing hit, and "the normal faces away from the light" would not do; the handle is t_k itself, computed with
+//      the statements of the pooled evaluation and therefore with the reference's bits.  l is bounded from below by the
+//      computed length of fl(P - L), which is within 4u of it (less 16u), dA from above with that length and |L|_1 (16u for
+//      the 10u); the sum t_k + dA rounds by u, inside the 16u.  The lane then counts the shadow ray (the frame's ray count is
+//      the reference's) and takes the second half of the shading block in the same trip: a lane spared only the walk would
+//      idle through it beside the wave's other lanes.
 // Forward rays (lam = 0, eps_o = 0, m = 0) are steps 1-3 unchanged.
 // The argument is checked the only way that counts: frames are compared bit for bit with the
 // oracle (tests/test_bvh_gpu.py: golden frames, random scenes over five orders of magnitude), and the walk, restated in
@@ -292,6 +306,29 @@ __device__ __forceinline__ void reversed_shadow_walk(bool shadow, v3 L, float li
         wd = V(-s.x, -s.y, -s.z);
         madd = slack;
     }
+}
+
+// Claim D of the header: is the shadow ray (L, s) towards the point a reflection ray has just reached on sphere k = (c, r2)
+// settled by k alone?  Yes when the reference's own test accepts k at a literal t_k that ends short of the shaded point by the
+// margin of claim A -- the ray enters k on its lit side, the point faces away from the light.  t_k is formed with the
+// statements of the pooled evaluation (trace_bvh: drain, HK:308-318), operation for operation, so it is bit for bit the t
+// the reference's loop computes for k: the literal form, chosen over a root-free bound because it needs no proof about
+// roundings of the root and the quotient and no register beyond this block.  len = fl|P - L| as normalize() formed it (within
+// 4u of |P - L|: 16u below it is a lower bound); len + |L|_1 >= (|P - L| + |L|)(1 - 4u), and 16u of that covers claim A's 10u.
+// Every comparison is written so that a NaN anywhere answers "no".
+#define RT_BVH_DEC_DELTA 0.0050011f                 /* >= 0.005001 of claim A, and the rounding of the sum it enters */
+#define RT_BVH_DEC_REL 9.5367431640625e-07f         /* 2^-20 = 16u */
+__device__ __forceinline__ bool shadow_decided(v3 L, float light_l1, v3 s, float len, v3 c, float r2) {
+    const float a2 = dot(s, s);                           // HK:308
+    const v3 oc = sub(L, c);
+    const float b = 2.0f * dot(s, oc);                    // HK:309
+    const float cc = dot(oc, oc) - r2;                    // HK:310
+    const float disc = b * b - (4.0f * a2) * cc;          // HK:311
+    if (!(disc > 0.0f && b < 0.0f)) return false;         // HK:316
+    const float tk = (-b - sqrtf(disc)) / (2.0f * a2);    // HK:317
+    const float d_a = __builtin_fmaf(len + light_l1, RT_BVH_DEC_REL, RT_BVH_DEC_DELTA);
+    const float l_lo = len * (1.0f - RT_BVH_DEC_REL);
+    return tk > 0.001f && tk < 9999.0f && tk + d_a <= l_lo;   // HK:318, and claim D
 }
 
 // Advances the walk of every lane's ray (o, d).  R/L: node records and links (LDS or global),
@@ -709,16 +746,23 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
             ++nrays;
 #endif
             const float next = affect + sum;                             // RK:120
+            // The two halves run one after the other, not either / or: A for the lanes whose reflection ray is complete, then
+            // B for the lanes whose shadow ray is complete AND for those whose shadow ray A has just settled without a walk
+            // (claim D of the header) -- such a lane starts its next reflection ray in this very trip.
+            const bool shadow_done = shadow;
+            bool decided = false;
             if (!shadow) {
                 // The centre and colour of the sphere a reflection ray has hit are requested HERE, by hand, and awaited
                 // where they are used: a wave issues in order, and the miss branch of the other lanes (three IEEE divisions)
                 // stands in between -- cycles the two loads used to add to every trip instead of sharing.  Lanes without a
                 // hit ask for sphere 0 and ignore the answer.
                 typedef float f3r __attribute__((ext_vector_type(3)));
-                f3r hit_g, hit_c;
+                typedef float f4r __attribute__((ext_vector_type(4)));
+                f4r hit_g;      // {c, r * r}: the fourth word is claim D's
+                f3r hit_c;
                 {
                     const uint32_t off = (uint32_t)(idx < 0 ? 0 : idx) << 4;
-                    asm volatile("global_load_dwordx3 %0, %2, %3\n\tglobal_load_dwordx3 %1, %2, %4"
+                    asm volatile("global_load_dwordx4 %0, %2, %3\n\tglobal_load_dwordx3 %1, %2, %4"
                                  : "=&v"(hit_g), "=&v"(hit_c) : "v"(off), "s"(A.geo), "s"(A.col) : "memory");
                 }
                 if (bounce == 0u) dist = idx >= 0 ? t : 0.0f;            // RK:116-118
@@ -737,16 +781,29 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
                 if (idx >= 0) {
                     albedo = V(hit_c.x, hit_c.y, hit_c.z);
                     const v3 pos = add(ro, scale(t, rd));                    // RK:129
-                    normal = normalize(sub(pos, V(hit_g.x, hit_g.y, hit_g.z)));   // HK:320
+                    const v3 centre = V(hit_g.x, hit_g.y, hit_g.z);
+                    normal = normalize(sub(pos, centre));                    // HK:320
                     ro = pos;
                     rd = normalize(reflect(rd, normal));                     // RK:130
-                    sdir = normalize(sub(ro, sc.lightPos));                  // RK:147
+                    const v3 dl = sub(ro, sc.lightPos);
+                    const float len = length(dl);
+                    sdir = divs(dl, len);                                    // RK:147: normalize(dl), its length kept for claim D
                     distance = length_of_unit(sdir);                         // RK:148
-                    shadow = true;                                           // RK:153 next
-                    node = 0u; t = 9999.0f; idx = -1;                        // shadow ray
+                    decided = shadow_decided(sc.lightPos, light_l1, sdir, len, centre, hit_g.w);
+                    if (!decided) {
+                        shadow = true;                                       // RK:153 next
+                        node = 0u; t = 9999.0f; idx = -1;                    // shadow ray
+                    }
+#ifdef RT_BVH_COUNT
+                    if (RT_BVH_COUNT == 16) nrays += decided ? 1u : 0u;      // shadow rays settled without a walk (lane)
+#else
+                    if (decided) ++nrays;                                    // the shadow ray the reference casts here: counted, not walked
+#endif
                 }
-            } else {
-                const float intensity = light_term(sc, ro, normal, sdir, distance, idx >= 0, t);
+            }
+            if (shadow_done || decided) {
+                // a settled shadow ray has a hit that is not at the shaded point: RK:165, like "no hit"
+                const float intensity = light_term(sc, ro, normal, sdir, distance, !decided && idx >= 0, t);
                 const v3 blended = scale(intensity, albedo);                 // RK:133-135
                 color = divs(add(scale(sum, color), scale(affect, blended)), next);   // RK:136
                 affect = affect / 2.0f;                                      // RK:139

@@ -15,5 +15,5 @@ wait
 /opt/rocm/bin/hipcc $FL -c tools/dev_dilate.hip -o /tmp/rtdev/dev_dilate.o
 /opt/rocm/lib/llvm/bin/llvm-objcopy --redefine-sym _Z20rt_launch_order_histPjS_S_jjPyS0_jS0_P12ihipStream_t=_Z25rt_launch_order_hist_origPjS_S_jjPyS0_jS0_P12ihipStream_t /tmp/rtdev/rt_triangles.o
 /opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o tools/bin/librt355_dev.so /tmp/rtdev/rt_api.o /tmp/rtdev/rt_bvh.o \
-    $CS/rt_kernels.o /tmp/rtdev/rt_triangles.o /tmp/rtdev/dev_dilate.o $CS/rt_assemble.o $CS/rt_comm.o -L/opt/rocm/lib -lrccl
+    $CS/rt_kernels.o /tmp/rtdev/rt_triangles.o /tmp/rtdev/dev_dilate.o $CS/rt_assemble.o $CS/rt_comm.o $CS/rt_query.o -L/opt/rocm/lib -lrccl
 ls -la tools/bin/*.so
