@@ -22,6 +22,7 @@ RT_KERNEL_HEATMAP = 1
 RT_MODE_FAST = 0
 RT_MODE_STRICT = 1
 RT_QUERY_LIMITS = 1      # flags of rt_trace_rays_ex / rt_occluded: ray words 3 and 7 are tmin and tmax
+RT_SHADE_COMPOSE = 1     # flags of rt_shade_rays: r, g, b is pixelColor (RK:91-96) instead of rayColor
 
 # every symbol include/rt355.h declares (tests check the library exports each of them)
 SYMBOLS = [
@@ -38,6 +39,7 @@ SYMBOLS = [
     "rt_trace_rays", "rt_trace_rays_host", "rt_pick",
     "rt_trace_rays_ex", "rt_trace_rays_host_ex", "rt_occluded", "rt_occluded_host",
     "rt_build_hierarchy_ex",
+    "rt_shade_rays", "rt_shade_rays_host",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -67,6 +69,15 @@ class RtHit(ctypes.Structure):
 
 # the same record as a numpy dtype: an (n,) array of it is what rt_trace_rays_host / rt_pick fill
 HIT_DTYPE = [("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("instance", "<i4"), ("normal", "<f4", (3,))]
+
+
+class RtShade(ctypes.Structure):
+    """rt_shade (include/rt355.h): the renderer's colour along one ray and the first segment's t, 16 bytes."""
+    _fields_ = [("r", ctypes.c_float), ("g", ctypes.c_float), ("b", ctypes.c_float), ("dist", ctypes.c_float)]
+
+
+# the same record as a numpy dtype: an (n,) array of it is what rt_shade_rays_host fills
+SHADE_DTYPE = [("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("dist", "<f4")]
 
 
 class RtError(RuntimeError):
@@ -173,6 +184,8 @@ def load():
         "rt_trace_rays_host_ex": (ctypes.c_int, [vp, vp, u32, u32, vp]),
         "rt_occluded": (ctypes.c_int, [vp, vp, u32, u32, vp, vp]),
         "rt_occluded_host": (ctypes.c_int, [vp, vp, u32, u32, vp]),
+        "rt_shade_rays": (ctypes.c_int, [vp, vp, u32, u32, vp, vp]),
+        "rt_shade_rays_host": (ctypes.c_int, [vp, vp, u32, u32, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -1607,6 +1607,86 @@ int rt_pick(rt_ctx* c, const uint32_t* xy, uint32_t n, rt_hit* hits) {
     return RT_OK;
 }
 
+// ---- shaded ray queries (rt_shade.hip) -----------------------------------------------------------------------------------------
+
+static_assert(sizeof(rt_shade) == 16, "rt_shade is one float4");
+
+// The argument checks of both forms, in query_device's order: flags, context, n == 0 (*done), pointers; then the state a shade
+// query reads beside the scene -- the parameters and the sky -- and the mesh texture a frame would default.
+static int shade_check(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, const rt_shade* out, bool device, bool& done) {
+    char msg[160];
+    done = false;
+    // (the flags first: a pure argument check, whatever the context)
+    if (flags & ~RT_SHADE_COMPOSE) { std::snprintf(msg, sizeof msg, "%s: unknown flag bits 0x%x", who, flags); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (n == 0) { done = true; return RT_OK; }
+    if (!rays || !out) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (device && (reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) % 16u) {
+        std::snprintf(msg, sizeof msg, "%s: rays and out must be 16-byte aligned", who);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    if (!c->have_params) { std::snprintf(msg, sizeof msg, "%s: rt_write_params has not been called", who); return fail(RT_ERR_STATE, msg); }
+    for (int i = 0; i < 6; ++i)
+        if (!c->d_face[i]) { std::snprintf(msg, sizeof msg, "%s: all six cube map faces must be written first", who); return fail(RT_ERR_STATE, msg); }
+    if (c->scene_kind == 1 && c->d_tri.used && !c->d_tex.used) {   // meshTex is mandatory in the reference (RR:113-114); default: 1x1 white
+        const uint8_t white[4] = {255, 255, 255, 255};
+        int rc = rt_write_mesh_texture(c, 1, 1, white);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
+// The shade kernel on `s` behind query_prepare: parameters, cube faces and sky flags as rt_enqueue assembles them for a frame,
+// by value in the kernel's arguments -- no slot of the event ring, no counters, no field of the stats.
+static int shade_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flags, float4* out, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+    RtFrameArgs fa;
+    std::memset(&fa, 0, sizeof fa);
+    std::memcpy(fa.p, c->params, sizeof fa.p);
+    fa.sky_flat = 1u;           // six 1x1 faces of one colour
+    fa.sky_seamless = 1u;       // six equal squares
+    for (int i = 0; i < 6; ++i) {
+        fa.face[i] = c->d_face[i]; fa.fw[i] = c->fw[i]; fa.fh[i] = c->fh[i];
+        if (c->fw[i] != 1u || c->fh[i] != 1u || c->face_texel0[i] != c->face_texel0[0]) fa.sky_flat = 0u;
+        if (c->fw[i] != c->fw[0] || c->fh[i] != c->fw[0]) fa.sky_seamless = 0u;
+    }
+    if (tri) RT_HIP(rt_launch_shade_triangles(fa, ts, inst, rays, flags, out, n, s));
+    else RT_HIP(rt_launch_shade_spheres(fa, c->d_records, c->n, rays, flags, out, n, s));
+    RT_HIP(hipEventRecord(c->ev_query, s));
+    c->query_pending = true;
+    c->query_last = s;
+    return RT_OK;
+}
+
+int rt_shade_rays(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, rt_shade* out, void* hip_stream) {
+    bool done;
+    { int rc = shade_check("rt_shade_rays", c, rays, n, flags, out, true, done); if (rc != RT_OK || done) return rc; }
+    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_shade_rays", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    return shade_launch(c, reinterpret_cast<const float4*>(rays), n, flags, reinterpret_cast<float4*>(out), s, tri, ts, inst);
+}
+
+int rt_shade_rays_host(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, rt_shade* out) {
+    bool done;
+    { int rc = shade_check("rt_shade_rays_host", c, rays, n, flags, out, false, done); if (rc != RT_OK || done) return rc; }
+    hipStream_t s;
+    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_shade_rays_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    const size_t bytes = (size_t)n * 32u, out_bytes = (size_t)n * sizeof(rt_shade);
+    { int rc = grow_staging(c->d_qrays, bytes); if (rc != RT_OK) return rc; }
+    { int rc = grow_staging(c->d_qhits, out_bytes); if (rc != RT_OK) return rc; }
+    RT_HIP(hipMemcpyAsync(c->d_qrays.p, rays, bytes, hipMemcpyHostToDevice, s));
+    { int rc = shade_launch(c, static_cast<const float4*>(c->d_qrays.p), n, flags, static_cast<float4*>(c->d_qhits.p), s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    RT_HIP(hipMemcpyAsync(out, c->d_qhits.p, out_bytes, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    return RT_OK;
+}
+
 int rt_device_pixels(rt_ctx* c, void** out_ptr, size_t* out_bytes) {
     if (!c || !out_ptr || !out_bytes) return fail(RT_ERR_INVALID_ARG, "rt_device_pixels: NULL argument");
     if (!c->d_out) return fail(RT_ERR_STATE, "rt_device_pixels: no colour buffer (rt_resize first)");

@@ -241,6 +241,11 @@ __device__ __forceinline__ uint32_t compose_pixel_sky(v3 sky, v3 color, float di
     const v3 px = add(scale(k, color), scale(1.0f - k, sky));
     return unorm8(px.x) | (unorm8(px.y) << 8) | (unorm8(px.z) << 16) | 0xFF000000u;
 }
+// ... and RK:91-96 alone: pixelColor before the rgba8unorm store (rt_shade.hip, RT_SHADE_COMPOSE)
+__device__ __forceinline__ v3 compose_color_sky(v3 sky, v3 color, float dist) {
+    const float k = clampf((30.0f - dist) / 30.0f, 0.0f, 1.0f);
+    return add(scale(k, color), scale(1.0f - k, sky));
+}
 __device__ __forceinline__ uint32_t compose_pixel(const RtFrameArgs& A, const Scene& sc, v3 dir0, v3 color, float dist) {
     return compose_pixel_sky(scale(sc.minIntensity, cube_sample(A, dir0)), color, dist);
 }

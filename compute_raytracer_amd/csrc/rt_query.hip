@@ -26,18 +26,10 @@
 #include "rt_tri_types.h"
 #include "rt_tri_device.h"
 #include "rt_filter.h"
+#include "rt_query_device.h"
 
 namespace rtk {
 
-constexpr int kQueryWaves = 4;
-constexpr uint32_t kQueryThreads = 64u * kQueryWaves;
-constexpr uint32_t kSphereChunk = 1024u;       // sphere records {centre, radius^2} staged per round: 16 KB of LDS
-
-__device__ __forceinline__ void load_ray(const float4* __restrict__ rays, size_t i, v3& o, v3& d) {
-    const float4 a = rays[2u * i], b = rays[2u * i + 1u];
-    o = V(a.x, a.y, a.z);
-    d = V(b.x, b.y, b.z);
-}
 // rt_hit: {t, u, v, prim}, {instance, normal.xyz}
 __device__ __forceinline__ void store_hit(float4* __restrict__ hits, size_t i, float t, float u, float v, int prim, int inst, v3 n) {
     hits[2u * i] = make_float4(t, u, v, __int_as_float(prim));

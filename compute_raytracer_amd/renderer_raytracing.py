@@ -253,6 +253,54 @@ class RendererRaytracing:
             cur.wait_stream(run)
         return out
 
+    # ---- shaded ray queries: the renderer's colour along the host's rays (rt_shade_rays / rt_shade_rays_host) -----------------
+    def shade_rays(self, origins, directions=None, compose=False, out=None):
+        """What the renderer would show along each ray, against the scene, light, sky and maxBounces the next frame would use
+        (recalculateScene() first, as render() does): {r, g, b, dist} = rayColor (RK:101-144), float32, not quantised; directions are
+        used as given and dist is in units of their length.  compose=True (RT_SHADE_COMPOSE): r, g, b is pixelColor (RK:91-96), the
+        fog towards the sky along the ray included -- a pixel's primary ray then gives that pixel of the next frame before its
+        rgba8 store.
+
+        numpy: origins and directions (n, 3) -> an (n, 4) float32 array, through rt_shade_rays_host.  torch: `origins` is a float32
+        (n, 8) tensor {origin, -, dir, -} on this renderer's device and `directions` is None -> an (n, 4) float32 tensor, or `out`,
+        enqueued through rt_shade_rays on torch.cuda.current_stream()."""
+        flags = abi.RT_SHADE_COMPOSE if compose else 0
+        if type(origins).__module__.split(".")[0] == "torch":
+            return self._shade_rays_torch(origins, directions, out, flags)
+        if out is not None:
+            raise ValueError("shade_rays: out= is for (n, 8) tensors")
+        rays = self._pack_rays(origins, directions, 0.0, 0.0)
+        self.recalculateScene()
+        res = np.zeros(rays.shape[0], dtype=abi.SHADE_DTYPE)
+        abi.check(self._lib.rt_shade_rays_host(self._ctx, rays.ctypes.data, rays.shape[0], flags, res.ctypes.data), self._ctx)
+        return res.view(np.float32).reshape(-1, 4)
+
+    def _shade_rays_torch(self, rays, directions, out, flags):
+        import torch
+        if directions is not None:
+            raise ValueError("shade_rays: a tensor argument is the (n, 8) ray buffer itself")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("shade_rays: rays must be a contiguous float32 (n, 8) tensor")
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise ValueError("shade_rays: rays must live on cuda:%d, this renderer's device" % self.device)
+        if out is None:
+            out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (rays.shape[0], 4) or not out.is_contiguous() or out.device != rays.device:
+            raise ValueError("shade_rays: out must be a contiguous float32 (n, 4) tensor on the rays' device")
+        self.recalculateScene()
+        cur = torch.cuda.current_stream(rays.device)
+        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
+        if cur.cuda_stream == 0:
+            if getattr(self, "_query_stream", None) is None:
+                self._query_stream = torch.cuda.Stream(rays.device)
+            run = self._query_stream
+            run.wait_stream(cur)
+        abi.check(self._lib.rt_shade_rays(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0], flags,
+                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(run.cuda_stream)), self._ctx)
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
     def pick(self, x, y):
         """What pixel (x, y) of the next frame sees first: its primary ray's nearest hit (full-frame coordinates, scalars or arrays
         that broadcast).  Triangle scenes add `mesh`, the instance's mesh index (-1 on a miss)."""

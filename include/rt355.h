@@ -326,6 +326,45 @@ int rt_trace_rays_host_ex(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t f
 int rt_occluded(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, uint8_t* occluded, void* hip_stream);  /* device, async */
 int rt_occluded_host(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, uint8_t* occluded);               /* host, sync   */
 
+/* ---- shaded ray queries: the renderer's colour along rays the host supplies (RK:101-144, optionally RK:91-96) -------------- */
+
+typedef struct rt_shade { float r, g, b, dist; } rt_shade;      /* 16 bytes */
+
+/* flags of rt_shade_rays */
+#define RT_SHADE_COMPOSE 1u   /* r, g, b is pixelColor (RK:91-96) instead of rayColor */
+
+/* rt_shade_rays / rt_shade_rays_host: what the renderer would show along each ray.  Rays are the 8-float records above
+ * {origin.xyz, -, dir.xyz, -}; words 3 and 7 are ignored.  Device form: `rays` and `out` ([n] rt_shade) in device memory of this
+ * context's GPU, 16-byte aligned, enqueued on `hip_stream` (NULL = the context's stream), returns at once.  Host form: host memory,
+ * synchronous, staged through the context's query buffers.
+ *
+ * flags = 0: out[i] is the vec4 rayColor(origin, dir) returns (RK:143).
+ *   - r, g, b: the running-mean colour after up to u32(maxBounces) bounces; every hit casts a shadow ray from the light
+ *     (RK:146-166); on a miss the sky is sampled along the path's last direction (RK:122-125).
+ *   - dist: the first segment's t (RK:116-118), or 0 when the first ray misses or maxBounces is 0.
+ *   - dir is used as given, nothing normalises it: dist is in units of |dir|.  From the first reflection on, directions are the
+ *     shader's own normalised ones.
+ * RT_SHADE_COMPOSE: r, g, b is instead pixelColor of RK:91-96 before the rgba8 store -- k = clamp((30 - dist) / 30, 0, 1),
+ * k * rayColor + (1 - k) * minIntensity * sky(dir as given); dist stays in word 3.  Shading pixel (x, y)'s primary ray (rt_pick's
+ * ray: RK:76-86) with this flag and quantising each channel by RK:98's rule (floor(clamp(c, 0, 1) * 255 + 0.5), NaN -> 0) gives
+ * exactly that pixel of the next frame.
+ *
+ * State read.  Light position, intensities and maxBounces are those of the last rt_write_params, copied at the call as a frame
+ * copies them: a later rt_write_params does not reach a query already enqueued.  The camera words are not read.  The sky and the mesh
+ * texture are what the next frame would sample (no mesh texture written: 1x1 white, as for a frame).
+ *
+ * Contract.  The contract of rt_trace_rays above applies word for word: a query sees every write made before it, per-frame instance
+ * writes that no frame has carried yet included; takes no slot of the event ring, changes no field of rt_stats, has no rt_kernel_id;
+ * is unaffected by rt_select_kernel, rt_set_mode and rt_set_variant; never disturbs frames in flight; queries run in call order, and
+ * scene writes after one wait for it.  Results are bit for bit the reference's arithmetic (the oracle's rt_oracle_ray_color for sphere
+ * scenes, its float frame for triangle scenes); sphere scenes are searched with the literal loop, every sphere in index order, for the
+ * path ray and the shadow ray alike.
+ *   - Unknown flag bits: RT_ERR_INVALID_ARG (checked first, whatever the context).  A NULL pointer: RT_ERR_INVALID_ARG.
+ *   - n == 0: RT_OK, nothing done.
+ *   - No scene written, no rt_write_params yet, or a cube map face missing: RT_ERR_STATE. */
+int rt_shade_rays(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, rt_shade* out, void* hip_stream);   /* device, async */
+int rt_shade_rays_host(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, rt_shade* out);                /* host, sync   */
+
 /* ---- multi-GPU: render + RCCL gather behind one call (RR:434-470 across a group of GPUs) ------ */
 
 /* One process per GPU.  Rank 0 calls rt_comm_unique_id and hands the bytes to the other ranks by

@@ -1,5 +1,5 @@
-"""Dev tool: the rate of ray queries -- nearest (rt_trace_rays), limited nearest (rt_trace_rays_ex with RT_QUERY_LIMITS) and
-occlusion (rt_occluded) -- beside the per-ray cost of an awaited frame of the reference's scene.
+"""Dev tool: the rate of ray queries -- nearest (rt_trace_rays), limited nearest (rt_trace_rays_ex with RT_QUERY_LIMITS),
+occlusion (rt_occluded) and shaded (rt_shade_rays) -- beside the per-ray cost of an awaited frame of the reference's scene.
 
     rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o q -- python tools/query_rate.py
 
@@ -9,7 +9,11 @@ runs REPS times through the device path on one stream, once per kind: "nearest" 
 9999, the same answers through the limited kernels) and "occluded" (the same limits); the kernel statistics of rocprofv3
 (query_triangles / query_spheres, limited_triangles / limited_spheres / occlude_spheres) give the rays per ms of the query
 kernels, and the line printed here gives the same from hipEvents around the batch.  The frame's
-figure is rt_stats.rays / kernel_ms of an awaited frame (RK:114 + RK:153 traversals, reflections and shadow rays included)."""
+figure is rt_stats.rays / kernel_ms of an awaited frame (RK:114 + RK:153 traversals, reflections and shadow rays included).
+"shade" is rt_shade_rays on the same rays (whole paths: rays_per_ms counts caller rays, not traversals; hit_fraction: dist > 0).
+"shade_vs_frame": the 2^20 primary rays of a 1024 x 1024 frame shaded with RT_SHADE_COMPOSE, beside kernel_ms of that frame
+through rt_render -- the same pixels by both routes -- on the reference's scene and on C3's spheres (the query searches the
+spheres by brute force, the frame walks the hierarchy)."""
 import json
 import os
 import sys
@@ -31,8 +35,8 @@ def ray_tensor(torch, o, d):
     return torch.from_numpy(rays).to("cuda:0")
 
 
-def camera(scene, W, H):
-    p = scene.pack_params(4)
+def camera(scene, W, H, bounces=4):
+    p = scene.pack_params(bounces)
     F = np.float32
     ys, xs = np.mgrid[0:H, 0:W]
     hc = (xs.reshape(-1).astype(F) - F(W) / F(2)) / F(W) * F(2)
@@ -55,6 +59,9 @@ def timed_one(torch, r, rays, kind):
     if kind == "occluded":
         out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
         run = lambda: r.occluded(rays, out=out)
+    elif kind == "shade":
+        out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
+        run = lambda: r.shade_rays(rays, out=out)
     else:
         out = torch.empty_like(rays)
         run = lambda: r.trace_rays(rays, out=out, limits=kind == "limited")
@@ -67,15 +74,43 @@ def timed_one(torch, r, rays, kind):
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / REPS
-    hits = int((out > 0).sum().item()) if kind == "occluded" else int((out[:, 3].view(torch.int32) >= 0).sum().item())
+    if kind == "occluded":
+        hits = int((out > 0).sum().item())
+    elif kind == "shade":
+        hits = int((out[:, 3] > 0).sum().item())
+    else:
+        hits = int((out[:, 3].view(torch.int32) >= 0).sum().item())
     return {"ms": round(ms, 4), "rays_per_ms": round(rays.shape[0] / ms), "hit_fraction": round(hits / rays.shape[0], 3)}
 
 
 def timed(torch, r, rays):
     res = {"rays": int(rays.shape[0])}
-    for kind in ("nearest", "limited", "occluded"):
+    for kind in ("nearest", "limited", "occluded", "shade"):
         res[kind] = timed_one(torch, r, rays, kind)
     return res
+
+
+def shade_vs_frame(torch, scene, bounces, mat):
+    """kernel_ms of an awaited 1024 x 1024 frame and the time of rt_shade_rays (RT_SHADE_COMPOSE) over its 2^20 primary rays"""
+    W = H = 1024
+    r = rt.RendererRaytracing(W, H, scene, maxBounces=bounces).initialize(None, mat)
+    for _ in range(5):
+        r.render()
+    st = r.stats()
+    rays = ray_tensor(torch, *camera(scene, W, H, bounces))
+    out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
+    r.shade_rays(rays, compose=True, out=out)
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(REPS):
+        r.shade_rays(rays, compose=True, out=out)
+    e1.record()
+    torch.cuda.synchronize()
+    ms = e0.elapsed_time(e1) / REPS
+    r.close()
+    return {"rays": int(rays.shape[0]), "frame_kernel_ms": round(st["kernel_ms"], 4), "frame_kernel": st["kernel_id"],
+            "shade_ms": round(ms, 4), "shade_rays_per_s": round(rays.shape[0] / ms * 1e3)}
 
 
 def main():
@@ -103,6 +138,8 @@ def main():
     lo, hi = (sp[:, 0:3] - sp[:, 7:8]).min(axis=0), (sp[:, 0:3] + sp[:, 7:8]).max(axis=0)
     out["c3_random_2^20"] = timed(torch, r, ray_tensor(torch, *random_rays(lo.astype(np.float64), hi.astype(np.float64), 1 << 20, 2)))
     r.close()
+    out["shade_vs_frame_ref"] = shade_vs_frame(torch, scene, int(d["maxBounces"]), rt.Material.white())
+    out["shade_vs_frame_c3"] = shade_vs_frame(torch, c3, cfg["bounces"], None)
     print(json.dumps(out))
 
 
