@@ -1577,6 +1577,68 @@ int rt_trace_rays_host(rt_ctx* c, const float* rays, uint32_t n, rt_hit* hits) {
     return query_host("rt_trace_rays_host", c, rays, n, 0u, false, hits);
 }
 
+// ---- the k nearest hits (rt_query.hip: multi_triangles, multi_spheres) ----
+
+// The argument checks of both forms, in the header's order: flags, k, context, n == 0 (*done), pointers
+static int multi_check(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, uint32_t k, const rt_hit* hits, bool device,
+                       bool& done) {
+    char msg[160];
+    done = false;
+    if (flags & ~RT_QUERY_LIMITS) { std::snprintf(msg, sizeof msg, "%s: unknown flag bits 0x%x", who, flags); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (k == 0u || k > RT355_MAX_HITS) {
+        std::snprintf(msg, sizeof msg, "%s: k = %u is outside 1 .. RT355_MAX_HITS (%u)", who, k, RT355_MAX_HITS);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (n == 0) { done = true; return RT_OK; }
+    if (!rays || !hits) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (device && (reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) % 16u) {
+        std::snprintf(msg, sizeof msg, "%s: rays and hits must be 16-byte aligned", who);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    return RT_OK;
+}
+
+static int multi_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flags, uint32_t k, float4* hits, hipStream_t s, bool tri,
+                        const RtTriScene& ts, int inst) {
+    if (tri) RT_HIP(rt_launch_multi_triangles(ts, inst, rays, flags, k, hits, n, s));
+    else RT_HIP(rt_launch_multi_spheres(c->d_records, c->n, rays, flags, k, hits, n, s));
+    RT_HIP(hipEventRecord(c->ev_query, s));
+    c->query_pending = true;
+    c->query_last = s;
+    return RT_OK;
+}
+
+int rt_trace_rays_multi(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, uint32_t k, rt_hit* hits, void* hip_stream) {
+    bool done;
+    { int rc = multi_check("rt_trace_rays_multi", c, rays, n, flags, k, hits, true, done); if (rc != RT_OK || done) return rc; }
+    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_trace_rays_multi", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    return multi_launch(c, reinterpret_cast<const float4*>(rays), n, flags, k, reinterpret_cast<float4*>(hits), s, tri, ts, inst);
+}
+
+int rt_trace_rays_multi_host(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, uint32_t k, rt_hit* hits) {
+    bool done;
+    { int rc = multi_check("rt_trace_rays_multi_host", c, rays, n, flags, k, hits, false, done); if (rc != RT_OK || done) return rc; }
+    hipStream_t s;
+    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_trace_rays_multi_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    const size_t bytes = (size_t)n * 32u, out_bytes = bytes * k;
+    { int rc = grow_staging(c->d_qrays, bytes); if (rc != RT_OK) return rc; }
+    { int rc = grow_staging(c->d_qhits, out_bytes); if (rc != RT_OK) return rc; }
+    RT_HIP(hipMemcpyAsync(c->d_qrays.p, rays, bytes, hipMemcpyHostToDevice, s));
+    { int rc = multi_launch(c, static_cast<const float4*>(c->d_qrays.p), n, flags, k, static_cast<float4*>(c->d_qhits.p), s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    RT_HIP(hipMemcpyAsync(hits, c->d_qhits.p, out_bytes, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    return RT_OK;
+}
+
 int rt_pick(rt_ctx* c, const uint32_t* xy, uint32_t n, rt_hit* hits) {
     if (!c) return fail(RT_ERR_INVALID_ARG, "rt_pick: ctx is NULL");
     if (n == 0) return RT_OK;

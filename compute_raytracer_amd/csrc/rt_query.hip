@@ -20,6 +20,9 @@
 //     triangle and writes one byte: no normal, no triangle lookup.  The same LDS as query_triangles.
 //   limited_spheres / occlude_spheres: the literal loop with exact_full<LIMITS>.  In occlude_spheres a lane stops testing at its
 //     first accepted sphere, and the workgroup stops staging chunks once none of its lanes is still searching.
+// The multi-hit form (rt_trace_rays_multi): the k nearest hits in the order (t, instance, prim), k records per ray.
+//   multi_triangles<K, ...>: multi_tlas (rt_tri_device.h) -- the same walk under the t of the lane's k-th hit, which it keeps with
+//     the others in a sorted register list of capacity K (4 or 8).  multi_spheres<K>: the literal loop into the same list.
 #include <type_traits>
 
 #include "rt_device.h"
@@ -226,6 +229,96 @@ __global__ __launch_bounds__(kQueryThreads) void occlude_spheres(const float* __
     occ[i] = idx >= 0 ? 1u : 0u;
 }
 
+// ---- the k nearest hits (rt_trace_rays_multi) ---------------------------------------------------------------------------------
+// hits [n][k] rt_hit: ray i's records at i*k .., sorted by (t, instance, prim), then miss records.  The list of a lane is a
+// HitList<K> in registers (rt_tri_device.h), K = 4 or 8 by k; LDS is limited_triangles' (both stacks and the staged head).
+
+// multi_tlas, then for each survivor what query_triangles stores for its winner: u and v are formed again by the arithmetic that
+// accepted the triangle (the same operations on the same operands: the same bits), the normal and the triangle index once each
+template <int K, typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
+__global__ __launch_bounds__(kQueryThreads) void multi_triangles(const RtTriScene T, const float4* __restrict__ rays, uint32_t flags,
+                                                                 uint32_t k, float4* __restrict__ hits, uint32_t n) {
+    typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
+    constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
+    __shared__ STK tstacks[kStack * kQueryThreads];
+    __shared__ BSTK bstacks[kStack * kQueryThreads];
+    __shared__ float4 s_nodes[2 * NODES];
+    __shared__ float s_blas[20 * BLAS];
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);
+    const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
+    if (i >= n) return;
+    v3 o, d;
+    float tmin, tmax;
+    load_ray_limits(rays, i, (flags & RT_QUERY_LIMITS) != 0u, o, d, tmin, tmax);
+    RtTriScene Tq = T;                             // (as in query_triangles)
+    if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
+    HitList<K, true> list;
+    multi_tlas<K, STK, PACKED, PAIRS, P16>(Tq, L, o, d, list, k, tstacks + threadIdx.x, bstacks + threadIdx.x, kQueryThreads, tmin, tmax);
+    for (uint32_t j = 0; j < k; ++j) {
+        TriHit h;
+        int prim;
+        list.get(j, h.t, h.blas, prim, h.tri);
+        if (h.tri < 0) { store_miss(hits, i * k + j); continue; }
+        const uint32_t bi = (uint32_t)h.blas;
+        const float* m = bi < L.n_blas ? L.blas + 20u * bi : T.blas + 20u * (size_t)bi;
+        v3 oo, od;
+        instance_ray(m, o, d, oo, od);
+        float t;
+        (void)triangle_tuv(T, (uint32_t)h.tri, oo, od, t, h.u, h.v);
+        const v3 nrm = hit_normal(T, h, m);
+        store_hit(hits, i * k + j, h.t, h.u, h.v, prim, h.blas, nrm);
+    }
+}
+
+// limited_spheres' loop; every sphere whose near root lies in (tmin, tmax) goes to the list (exact_full against tmax alone is that
+// acceptance, and leaves the root in `t`)
+template <int K>
+__global__ __launch_bounds__(kQueryThreads) void multi_spheres(const float* __restrict__ records, uint32_t n_spheres,
+                                                               const float4* __restrict__ rays, uint32_t flags, uint32_t k,
+                                                               float4* __restrict__ hits, uint32_t n) {
+    __shared__ float4 s_geo[kSphereChunk];
+    const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
+    const bool live = i < n;                       // every lane stages: no return before the last barrier
+    v3 o = V(0.0f, 0.0f, 0.0f), d = V(0.0f, 0.0f, 0.0f);
+    float tmin = 0.001f, tmax = 9999.0f;
+    if (live) load_ray_limits(rays, i, (flags & RT_QUERY_LIMITS) != 0u, o, d, tmin, tmax);
+    const float a = dot(d, d);                     // HK:308
+    const float fa = 4.0f * a;                     // the (4*a) of HK:311
+    const float ta = 2.0f * a;                     // HK:317
+    HitList<K, false> list;
+    list.init(tmax);
+    for (uint32_t base = 0; base < n_spheres; base += kSphereChunk) {
+        const uint32_t m = n_spheres - base < kSphereChunk ? n_spheres - base : kSphereChunk;
+        __syncthreads();                           // the previous chunk is done with
+        for (uint32_t q = threadIdx.x; q < m; q += kQueryThreads) {
+            const float4* r = reinterpret_cast<const float4*>(records + 8u * ((size_t)base + q));
+            const float4 c = r[0], w = r[1];
+            s_geo[q] = make_float4(c.x, c.y, c.z, w.w * w.w);       // radius * radius (HK:310)
+        }
+        __syncthreads();
+        if (live) {
+            for (uint32_t q = 0; q < m; ++q) {
+                const float4 g = s_geo[q];
+                float t = tmax;
+                int idx = -1;
+                exact_full<false, true>(V(g.x, g.y, g.z), g.w, (int)(base + q), o, d, fa, ta, t, idx, tmin);
+                if (idx >= 0 && t <= list.bound) list.insert(k, t, 0, idx, 0);
+            }
+        }
+    }
+    if (!live) return;
+    for (uint32_t j = 0; j < k; ++j) {
+        float t;
+        int idx, unused_inst, unused_slot;
+        list.get(j, t, unused_inst, idx, unused_slot);
+        if (idx == 0x7FFFFFFF) { store_miss(hits, i * k + j); continue; }
+        const float* s = records + 8u * (size_t)idx;
+        const v3 position = add(o, scale(t, d));                           // HK:319
+        const v3 nrm = normalize(sub(position, V(s[0], s[1], s[2])));       // HK:320
+        store_hit(hits, i * k + j, t, 0.0f, 0.0f, idx, -1, nrm);
+    }
+}
+
 // the primary ray of pixel (x, y) (RK:76-86): the ray that pixel of the next frame starts with
 __global__ __launch_bounds__(256) void pick_rays(const RtFrameArgs A, const uint32_t* __restrict__ xy, float4* __restrict__ rays, uint32_t n) {
     const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
@@ -270,7 +363,47 @@ static void launch_lt_form(const RtTriScene& t, int inst, const float4* rays, ui
     else                   launch_lt_walk<false, ANY>(t, rays, flags, out, n, s);
 }
 
+template <int K, typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
+static void launch_mt(const RtTriScene& t, const float4* rays, uint32_t flags, uint32_t k, float4* hits, uint32_t n, hipStream_t s) {
+    const uint32_t blocks = (uint32_t)(((size_t)n + kQueryThreads - 1u) / kQueryThreads);
+    hipLaunchKernelGGL((multi_triangles<K, STK, PACKED, PAIRS, P16, INST>), dim3(blocks), dim3(kQueryThreads), 0, s, t, rays, flags, k, hits, n);
+}
+template <int K, bool INST>
+static void launch_mt_walk(const RtTriScene& t, const float4* rays, uint32_t flags, uint32_t k, float4* hits, uint32_t n, hipStream_t s) {
+    if (t.n_nodes <= 65536u && t.packed_ok) launch_mt<K, uint16_t, true, false, false, INST>(t, rays, flags, k, hits, n, s);
+    else if (t.n_nodes <= 65536u)          launch_mt<K, uint16_t, false, false, false, INST>(t, rays, flags, k, hits, n, s);
+    else                                   launch_mt<K, uint32_t, false, false, false, INST>(t, rays, flags, k, hits, n, s);
+}
+// the forms of launch_lt_form
+template <int K>
+static void launch_mt_form(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, uint32_t k, float4* hits, uint32_t n, hipStream_t s) {
+    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= kWideBlas;
+    if (pairs && t.p16_ok) launch_mt<K, uint16_t, true, true, true, true>(t, rays, flags, k, hits, n, s);
+    else if (pairs)        launch_mt<K, uint16_t, true, true, false, true>(t, rays, flags, k, hits, n, s);
+    else if (inst)         launch_mt_walk<K, true>(t, rays, flags, k, hits, n, s);
+    else                   launch_mt_walk<K, false>(t, rays, flags, k, hits, n, s);
+}
+
 }  // namespace rtk
+
+hipError_t rt_launch_multi_triangles(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, uint32_t k, float4* hits,
+                                     uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (k == 0 || k > RT355_MAX_HITS) return hipErrorInvalidValue;
+    if (k <= 4u) rtk::launch_mt_form<4>(t, inst, rays, flags, k, hits, n, s);
+    else         rtk::launch_mt_form<8>(t, inst, rays, flags, k, hits, n, s);
+    return hipGetLastError();
+}
+
+hipError_t rt_launch_multi_spheres(const float* records, uint32_t n_spheres, const float4* rays, uint32_t flags, uint32_t k, float4* hits,
+                                   uint32_t n, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    if (k == 0 || k > RT355_MAX_HITS) return hipErrorInvalidValue;
+    const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
+    if (k <= 4u) hipLaunchKernelGGL(rtk::multi_spheres<4>, dim3(blocks), dim3(rtk::kQueryThreads), 0, s, records, n_spheres, rays, flags, k, hits, n);
+    else         hipLaunchKernelGGL(rtk::multi_spheres<8>, dim3(blocks), dim3(rtk::kQueryThreads), 0, s, records, n_spheres, rays, flags, k, hits, n);
+    return hipGetLastError();
+}
 
 hipError_t rt_launch_query_triangles(const RtTriScene& t, int inst, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;

@@ -110,13 +110,10 @@ __device__ __forceinline__ uint32_t tri_of(const RtTriScene& T, int slot) {
     return ti >= T.n_tri ? T.n_tri - 1u : ti;
 }
 
-// RK:344-381, up to the acceptance test; normal / uv / colour are formed later for the winner.
+// RK:344-379: hitTriangle's tests (back faces culled) and its t, u, v, before the limits of RK:380 -- which the caller applies.
 // `slot` is the position in the triangle lookup table (RK:314: triangles[u32(triangleLookup[i + left])]); the three
 // corners of that triangle come from T.corners, the library's own compact copy in lookup order (rt_tri_corners below).
-// LIMITS (ray queries with RT_QUERY_LIMITS): `tMin` replaces the reference's 0.001.
-template <bool LIMITS = false>
-__device__ __forceinline__ bool hit_triangle(const RtTriScene& T, uint32_t slot, v3 o, v3 d, float tMax,
-                                             float& t_out, float& u_out, float& v_out, float tMin = 0.0f) {
+__device__ __forceinline__ bool triangle_tuv(const RtTriScene& T, uint32_t slot, v3 o, v3 d, float& t_out, float& u_out, float& v_out) {
     const float4* tr = T.corners + 3u * (size_t)slot;
     const float4 A = tr[0], B = tr[1], C = tr[2];
     const v3 cornerA = V(A.x, A.y, A.z);
@@ -135,6 +132,17 @@ __device__ __forceinline__ bool hit_triangle(const RtTriScene& T, uint32_t slot,
     const float t = invDet * dot(edge2, sCrossEdge1);               // RK:377
     u = u * invDet;                                                 // RK:378
     v = v * invDet;                                                 // RK:379
+    t_out = t; u_out = u; v_out = v;
+    return true;
+}
+
+// RK:344-381, up to the acceptance test; normal / uv / colour are formed later for the winner.
+// LIMITS (ray queries with RT_QUERY_LIMITS): `tMin` replaces the reference's 0.001.
+template <bool LIMITS = false>
+__device__ __forceinline__ bool hit_triangle(const RtTriScene& T, uint32_t slot, v3 o, v3 d, float tMax,
+                                             float& t_out, float& u_out, float& v_out, float tMin = 0.0f) {
+    float t, u, v;
+    if (!triangle_tuv(T, slot, o, d, t, u, v)) return false;
     if (t > (LIMITS ? tMin : 0.001f) && t < tMax) {                 // RK:380 (tMin 0.001, RK:315)
         t_out = t; u_out = u; v_out = v;
         return true;
@@ -339,6 +347,217 @@ __device__ __forceinline__ TriHit trace_tlas(const RtTriScene& T, const TriLds& 
         }
     }
     return hit;
+}
+
+// ---- multi-hit ray queries (rt_trace_rays_multi): the k nearest hits instead of the nearest --------------------------------------
+// A lane's k smallest hits so far under the total order (t, instance, prim), ascending, in registers: K is a compile-time
+// capacity and every index below is one, so nothing here is addressed dynamically (no scratch); the k <= K in use is uniform.
+// An unused entry is (tmax, INT_MAX, INT_MAX): every accepted hit (t < tmax) sorts before it, and `bound` -- the t of entry k-1 --
+// is tmax until the list is full and the k-th hit's t afterwards, with no count to keep.  TRI: entries carry the instance and the
+// triangle-lookup slot (u and v are formed again for the survivors); spheres order by (t, index) alone.
+template <int K, bool TRI>
+struct HitList {
+    float t[K];
+    int prim[K], inst[K], slot[K];
+    float bound;
+    __device__ __forceinline__ void init(float tmax) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) { t[j] = tmax; prim[j] = 0x7FFFFFFF; inst[j] = 0x7FFFFFFF; slot[j] = -1; }
+        bound = tmax;
+    }
+    // Inserts (et, ei, ep) where it sorts; the former entry k-1 falls out.  A key the list already holds is dropped: a walk whose
+    // clamped stack brings it to a leaf twice still reports that hit once.
+    __device__ __forceinline__ void insert(uint32_t k, float et, int ei, int ep, int es) {
+#pragma unroll
+        for (int j = 0; j < K; ++j) {
+            if ((uint32_t)j < k) {
+                const bool tie = et == t[j];
+                const bool held = tie && ep == prim[j] && (!TRI || ei == inst[j]);
+                const bool before = et < t[j] || (tie && (TRI ? (ei < inst[j] || (ei == inst[j] && ep < prim[j])) : ep < prim[j]));
+                if (before) {
+                    const float ft = t[j]; t[j] = et; et = ft;
+                    const int fp = prim[j]; prim[j] = ep; ep = fp;
+                    if (TRI) {
+                        const int fi = inst[j]; inst[j] = ei; ei = fi;
+                        const int fs = slot[j]; slot[j] = es; es = fs;
+                    }
+                } else if (held) {
+                    et = __builtin_inff(); ei = 0x7FFFFFFF; ep = 0x7FFFFFFF;    // sorts before nothing from here on
+                }
+                if ((uint32_t)j + 1u == k) bound = t[j];
+            }
+        }
+    }
+    __device__ __forceinline__ void get(uint32_t j, float& et, int& ei, int& ep, int& es) const {
+        et = t[0]; ep = prim[0]; ei = inst[0]; es = slot[0];
+#pragma unroll
+        for (int q = 1; q < K; ++q)
+            if ((uint32_t)q == j) { et = t[q]; ep = prim[q]; ei = inst[q]; es = slot[q]; }
+    }
+};
+
+// RK:254-255: the ray in the object space of the instance whose record is m (inverseModel, column-major)
+__device__ __forceinline__ void instance_ray(const float* m, v3 o, v3 d, v3& oo, v3& od) {
+    oo = V(((m[0] * o.x + m[4] * o.y) + m[8] * o.z) + m[12] * 1.0f,
+           ((m[1] * o.x + m[5] * o.y) + m[9] * o.z) + m[13] * 1.0f,
+           ((m[2] * o.x + m[6] * o.y) + m[10] * o.z) + m[14] * 1.0f);
+    od = V(((m[0] * d.x + m[4] * d.y) + m[8] * d.z) + m[12] * 0.0f,
+           ((m[1] * d.x + m[5] * d.y) + m[9] * d.z) + m[13] * 0.0f,
+           ((m[2] * d.x + m[6] * d.y) + m[10] * d.z) + m[14] * 0.0f);
+}
+
+// trace_blas for the k nearest: the same walk (near child first, the same stack forms and clamps) under list.bound.  A box is left
+// out only when its entry distance is strictly beyond the bound, and the far child is pushed at `<=` where RK:303 has `<`: a
+// triangle at exactly the k-th t may still sort before the k-th entry by (instance, prim).  Every triangle hit_triangle's tests
+// pass with tmin < t < tmax (both strict) and t <= bound goes to the list, which decides.
+template <int K, typename STK, bool PACKED, bool PAIRS, bool P16>
+__device__ __forceinline__ void multi_blas(const RtTriScene& T, const TriLds& L, uint32_t bi, v3 o, v3 d, HitList<K, true>& list, uint32_t k,
+                                           typename std::conditional<PACKED && !P16, uint32_t, STK>::type* stack, uint32_t stride,
+                                           float tmin, float tmax) {
+    typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
+    auto pack16 = [](uint32_t m) -> uint32_t { return ((m >> 16) << 14) | (m & 0x3FFFu); };
+    auto unpack16 = [](uint32_t e) -> uint32_t { return ((e >> 14) << 16) | (e & 0x3FFFu); };
+    auto leaf = [&](uint32_t left, uint32_t count, v3 oo, v3 od) {  // RK:311-321
+        for (uint32_t i = 0; i < count; ++i) {
+            uint32_t li = i + left;
+            if (li >= T.n_tri_lookup) li = T.n_tri_lookup - 1u;
+            float t, u, v;
+            if (triangle_tuv(T, li, oo, od, t, u, v) && t > tmin && t < tmax && t <= list.bound)
+                list.insert(k, t, (int)bi, (int)tri_of(T, (int)li), (int)li);
+        }
+    };
+    float m[17];                                                    // (as in trace_blas)
+    if (bi < L.n_blas) {
+#pragma unroll
+        for (int q = 0; q < 17; ++q) m[q] = L.blas[20u * bi + (uint32_t)q];
+    } else {
+        const float* g = T.blas + 20u * (size_t)bi;
+#pragma unroll
+        for (int q = 0; q < 17; ++q) m[q] = g[q];
+    }
+    v3 oo, od;
+    instance_ray(m, o, d, oo, od);
+    const v3 inv = V(1.0f / od.x, 1.0f / od.y, 1.0f / od.z);        // RK:396
+    if (PAIRS) {
+        uint32_t pnode = __float_as_uint(L.blas[20u * bi + 17u]);
+        uint32_t psp = 0;
+        for (;;) {
+            const uint32_t count = pnode >> 16, left = pnode & 0xFFFFu;
+            if (count == 0u) {
+                const float4* g = T.pairs + 4u * (size_t)left;
+                const float4 q0 = g[0], q1 = g[1], q2 = g[2], q3 = g[3];
+                NodeR c1, c2;
+                c1.lo = V(q0.x, q0.y, q0.z); c1.hi = V(q1.x, q1.y, q1.z);
+                c2.lo = V(q2.x, q2.y, q2.z); c2.hi = V(q3.x, q3.y, q3.z);
+                const uint32_t m1 = __float_as_uint(q0.w), m2 = __float_as_uint(q2.w);
+                float d1 = hit_aabb(oo, inv, c1);
+                float d2 = hit_aabb(oo, inv, c2);
+                const bool swap = d1 > d2;
+                if (swap) { const float tmp = d1; d1 = d2; d2 = tmp; }
+                if (d1 > list.bound) {
+                    if (psp == 0u) break;
+                    psp -= 1u;
+                    pnode = P16 ? unpack16(stack[sclamp(psp) * stride]) : (uint32_t)stack[sclamp(psp) * stride];
+                } else {
+                    pnode = swap ? m2 : m1;
+                    if (d2 <= list.bound) {
+                        stack[sclamp(psp) * stride] = (BSTK)(P16 ? pack16(swap ? m1 : m2) : (swap ? m1 : m2));
+                        psp += 1u;
+                    }
+                }
+            } else {
+                leaf(left, count, oo, od);
+                if (psp == 0u) break;
+                psp -= 1u;
+                pnode = P16 ? unpack16(stack[sclamp(psp) * stride]) : (uint32_t)stack[sclamp(psp) * stride];
+            }
+        }
+        return;
+    }
+    NodeR node = load_node(T, u32f(m[16]));                         // RK:265
+    uint32_t sp = 0;
+    for (;;) {
+        const uint32_t count = u32f(node.count);
+        const uint32_t left = u32f(node.left);
+        if (count == 0u) {
+            uint32_t i2 = left + 1u;
+            NodeR c1 = load_node(T, left), c2 = load_node(T, left + 1u);
+            asm volatile("" : "+v"(c1.left), "+v"(c1.count), "+v"(c2.left), "+v"(c2.count));   // (as in trace_blas)
+            float d1 = hit_aabb(oo, inv, c1);
+            float d2 = hit_aabb(oo, inv, c2);
+            const bool swap = d1 > d2;
+            if (swap) { const float tmp = d1; d1 = d2; d2 = tmp; i2 = left; }
+            if (d1 > list.bound) {
+                if (sp == 0u) break;
+                sp -= 1u;
+                if (PACKED) { const uint32_t e = stack[sclamp(sp) * stride]; node.count = (float)(e >> 16); node.left = (float)(e & 0xFFFFu); }
+                else node = load_node(T, stack[sclamp(sp) * stride]);
+            } else {
+                node = swap ? c2 : c1;
+                if (d2 <= list.bound) {
+                    if (PACKED) {
+                        const uint32_t fc = u32f(swap ? c1.count : c2.count), fl = u32f(swap ? c1.left : c2.left);
+                        stack[sclamp(sp) * stride] = ((fc < 0xFFFFu ? fc : 0xFFFFu) << 16) | (fl < 0xFFFFu ? fl : 0xFFFFu);
+                    } else {
+                        stack[sclamp(sp) * stride] = (STK)(i2 < T.n_nodes ? i2 : T.n_nodes - 1u);
+                    }
+                    sp += 1u;
+                }
+            }
+        } else {
+            leaf(left, count, oo, od);
+            if (sp == 0u) break;
+            sp -= 1u;
+            if (PACKED) { const uint32_t e = stack[sclamp(sp) * stride]; node.count = (float)(e >> 16); node.left = (float)(e & 0xFFFFu); }
+            else node = load_node(T, stack[sclamp(sp) * stride]);
+        }
+    }
+}
+
+// trace_tlas for the k nearest (twenty top-level slots, the guard of RK:212): fills `list`; the pruning rule is multi_blas's
+template <int K, typename STK, bool PACKED, bool PAIRS, bool P16>
+__device__ __forceinline__ void multi_tlas(const RtTriScene& T, const TriLds& L, v3 o, v3 d, HitList<K, true>& list, uint32_t k, STK* tstack,
+                                           typename std::conditional<PACKED && !P16, uint32_t, STK>::type* bstack, uint32_t stride,
+                                           float tmin, float tmax) {
+    list.init(tmax);
+    const v3 inv = V(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
+    NodeR node = load_node_head(T, L, 0u);                          // RK:175
+    uint32_t sp = 0;
+    for (;;) {
+        const uint32_t count = u32f(node.count);
+        const uint32_t left = u32f(node.left);
+        if (count == 0u) {
+            uint32_t i2 = left + 1u;
+            const NodeR c1 = load_node_head(T, L, left), c2 = load_node_head(T, L, left + 1u);
+            float d1 = hit_aabb(o, inv, c1);
+            float d2 = hit_aabb(o, inv, c2);
+            const bool swap = d1 > d2;
+            if (swap) { const float tmp = d1; d1 = d2; d2 = tmp; i2 = left; }
+            if (d1 > list.bound) {
+                if (sp == 0u) break;
+                sp -= 1u;
+                node = load_node_head(T, L, tstack[tclamp<kStack>(sp) * stride]);
+            } else {
+                node = swap ? c2 : c1;
+                if (d2 <= list.bound) {
+                    tstack[tclamp<kStack>(sp) * stride] = (STK)(i2 < T.n_nodes ? i2 : T.n_nodes - 1u);
+                    sp += 1u;
+                    if (sp > kStack) sp = kStack - 1u;              // RK:212-214
+                }
+            }
+        } else {
+            for (uint32_t i = 0; i < count; ++i) {                  // RK:220
+                uint32_t li = i + left;
+                if (li >= T.n_blas_lookup) li = T.n_blas_lookup - 1u;
+                uint32_t bi = u32f(li < L.n_lookup ? L.blas[20u * li + 19u] : T.blas_lookup[li]);   // RK:223
+                if (bi >= T.n_blas) bi = T.n_blas - 1u;
+                multi_blas<K, STK, PACKED, PAIRS, P16>(T, L, bi, o, d, list, k, bstack, stride, tmin, tmax);
+            }
+            if (sp == 0u) break;
+            sp -= 1u;
+            node = load_node_head(T, L, tstack[tclamp<kStack>(sp) * stride]);
+        }
+    }
 }
 
 // What hitTriangle (RK:381-387) and traceBLAS (RK:334-338) attach to the accepted hit -- in two parts, so that

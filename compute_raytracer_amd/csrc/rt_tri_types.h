@@ -66,6 +66,11 @@ hipError_t rt_launch_limited_triangles(const RtTriScene& t, int inst, const floa
                                        uint32_t n, hipStream_t s);
 hipError_t rt_launch_limited_spheres(const float* records, uint32_t n_spheres, const float4* rays, uint32_t flags, bool any, void* out,
                                      uint32_t n, hipStream_t s);
+// The k nearest hits (rt_trace_rays_multi), 1 <= k <= RT355_MAX_HITS: hits [n][k] rt_hit, sorted, then miss records
+hipError_t rt_launch_multi_triangles(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, uint32_t k, float4* hits,
+                                     uint32_t n, hipStream_t s);
+hipError_t rt_launch_multi_spheres(const float* records, uint32_t n_spheres, const float4* rays, uint32_t flags, uint32_t k, float4* hits,
+                                   uint32_t n, hipStream_t s);
 // Shaded ray queries (rt_shade.hip; include/rt355.h: rt_shade_rays): out [n] float4 {r, g, b, dist}.  `a`: parameters, cube faces and
 // sky flags as a frame's arguments hold them (nothing else of it is read); flags: RT_SHADE_COMPOSE.  inst as above.
 hipError_t rt_launch_shade_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const float4* rays, uint32_t flags, float4* out,

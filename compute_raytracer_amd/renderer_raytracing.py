@@ -253,6 +253,59 @@ class RendererRaytracing:
             cur.wait_stream(run)
         return out
 
+    # ---- multi-hit queries: the k nearest hits of the host's rays (rt_trace_rays_multi / rt_trace_rays_multi_host) -------------
+    def trace_rays_multi(self, origins, directions=None, k=4, tmin=None, tmax=None, limits=False, out=None):
+        """The first k surfaces each ray crosses (1 <= k <= abi.RT355_MAX_HITS), sorted by (t, instance, prim); the conventions
+        are trace_rays'.
+
+        numpy: origins and directions (n, 3), `tmin` / `tmax` scalars or (n,) arrays -> dict of arrays t, u, v, prim, instance
+        (n, k) and normal (n, k, 3), unused places holding the miss record, plus `count` (n,), the number of hits of each ray.
+        torch: a float32 (n, 8) tensor {origin, tmin, dir, tmax} on this renderer's device (`limits=True` reads words 3 and 7)
+        -> an (n, k, 8) float32 tensor of rt_hit records, or `out`, enqueued on torch.cuda.current_stream()."""
+        k = int(k)
+        if type(origins).__module__.split(".")[0] == "torch":
+            if tmin is not None or tmax is not None:
+                raise ValueError("trace_rays_multi: with a tensor the limits are words 3 and 7 of the rays (limits=True)")
+            return self._trace_rays_multi_torch(origins, directions, k, abi.RT_QUERY_LIMITS if limits else 0, out)
+        if limits:
+            raise ValueError("trace_rays_multi: limits=True is for (n, 8) tensors; numpy rays take tmin / tmax")
+        if out is not None:
+            raise ValueError("trace_rays_multi: out= is for (n, 8) tensors")
+        flags = abi.RT_QUERY_LIMITS if (tmin is not None or tmax is not None) else 0
+        rays = self._pack_rays(origins, directions, 0.001 if tmin is None else tmin, 9999.0 if tmax is None else tmax)
+        self.recalculateScene()
+        hits = np.zeros((rays.shape[0], max(k, 0)), dtype=abi.HIT_DTYPE)
+        abi.check(self._lib.rt_trace_rays_multi_host(self._ctx, rays.ctypes.data, rays.shape[0], flags, k, hits.ctypes.data), self._ctx)
+        res = self._hit_dict(hits)
+        res["count"] = (hits["prim"] >= 0).sum(axis=1)
+        return res
+
+    def _trace_rays_multi_torch(self, rays, directions, k, flags, out):
+        import torch
+        if directions is not None:
+            raise ValueError("trace_rays_multi: a tensor argument is the (n, 8) ray buffer itself")
+        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
+            raise ValueError("trace_rays_multi: rays must be a contiguous float32 (n, 8) tensor")
+        if rays.device.type != "cuda" or rays.device.index != self.device:
+            raise ValueError("trace_rays_multi: rays must live on cuda:%d, this renderer's device" % self.device)
+        if out is None:
+            out = torch.empty((rays.shape[0], max(k, 0), 8), dtype=torch.float32, device=rays.device)
+        elif out.element_size() != 4 or tuple(out.shape) != (rays.shape[0], k, 8) or not out.is_contiguous() or out.device != rays.device:
+            raise ValueError("trace_rays_multi: out must be a contiguous 32-bit (n, k, 8) tensor on the rays' device")
+        self.recalculateScene()
+        cur = torch.cuda.current_stream(rays.device)
+        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
+        if cur.cuda_stream == 0:
+            if getattr(self, "_query_stream", None) is None:
+                self._query_stream = torch.cuda.Stream(rays.device)
+            run = self._query_stream
+            run.wait_stream(cur)
+        abi.check(self._lib.rt_trace_rays_multi(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0], flags, k,
+                                                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(run.cuda_stream)), self._ctx)
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
     # ---- shaded ray queries: the renderer's colour along the host's rays (rt_shade_rays / rt_shade_rays_host) -----------------
     def shade_rays(self, origins, directions=None, compose=False, out=None):
         """What the renderer would show along each ray, against the scene, light, sky and maxBounces the next frame would use

@@ -326,6 +326,48 @@ int rt_trace_rays_host_ex(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t f
 int rt_occluded(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, uint8_t* occluded, void* hip_stream);  /* device, async */
 int rt_occluded_host(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, uint8_t* occluded);               /* host, sync   */
 
+/* ---- multi-hit queries: the k nearest hits along each ray -------------------------------------------------------------------- */
+
+#define RT355_MAX_HITS 8u    /* the largest k of rt_trace_rays_multi */
+
+/* rt_trace_rays_multi / rt_trace_rays_multi_host: the first k surfaces each ray crosses, in order.  `rays` are the 8-float records
+ * above; `flags` is 0 or RT_QUERY_LIMITS with exactly rt_trace_rays_ex's meaning (words 3 and 7 are tmin and tmax, otherwise 0.001
+ * and 9999).  `hits` is [n][k] rt_hit: ray i's records are hits[i*k .. i*k+k), the filled ones first in the order below, the rest the
+ * miss record of rt_trace_rays (t = -1, prim = instance = -1, everything else 0).  There is no count array: count prim >= 0.
+ * Device form: `rays` and `hits` in device memory of this context's GPU, 16-byte aligned, enqueued on `hip_stream` (NULL = the
+ * context's stream), returns at once.  Host form: host memory, synchronous, staged through the context's query buffers (which grow
+ * to n*k*32 bytes for the hits).
+ *
+ * Which hits.
+ *   - Triangle scenes: a hit is a pair of an instance and a triangle-lookup slot under that instance's BLAS root that passes
+ *     hitTriangle's tests (RK:344-379, back faces culled) with tmin < t < tmax, both strict.  t, u, v and the normal are exactly
+ *     rt_trace_rays' for that triangle and instance; t is the world ray parameter, so hits of different instances compare.
+ *   - Sphere scenes: a hit is a sphere whose near root (HK:316-317, disc > 0) lies in (tmin, tmax): at most one hit per sphere,
+ *     and a ray that starts inside a sphere does not see it, as in the reference.
+ *   - Reported are the k smallest under the total order ascending t, then ascending instance, then ascending prim (spheres: t, then
+ *     index), sorted by it.  The result does not depend on the order the walk visits things: surfaces at exactly equal t
+ *     (coincident instances, duplicated spheres) are all kept, which calling rt_trace_rays_ex again with tmin = t cannot do.
+ *
+ * Pruning.  The bound is tmax while a ray holds fewer than k hits and the t of its k-th hit afterwards.  A box is skipped only
+ * when its entry distance is strictly greater than the bound, and the far child is visited when its distance is <= the bound (the
+ * reference's nearest search has <): a surface at exactly the k-th t that sorts before the k-th entry replaces it.  The note on
+ * tmax >= 99999 of rt_trace_rays_ex applies unchanged.
+ *
+ * Relation to the other queries.  On a scene whose trees the reference's walk searches exhaustively (every tree the library's and
+ * the reference's builders make), hit 0's t is bit for bit rt_trace_rays_ex's t, the miss sets agree, and rt_occluded is 1 exactly
+ * where hit 0 exists.  On an exact tie hit 0 may name a different triangle than rt_trace_rays_ex, whose winner depends on the
+ * order of its walk; for spheres it names the same one, the lowest index.
+ * On hand-made trees the walk does not search exhaustively (a spine deeper than the twenty stack slots, boxes that do not nest)
+ * the walk clamps its stacks as the nearest search does and is memory-safe; its records are still true hits, distinct, sorted and
+ * within the limits, and it promises no more than that.
+ *
+ * Checks, in this order: unknown flag bits, then k == 0 or k > RT355_MAX_HITS, then a NULL context: RT_ERR_INVALID_ARG;
+ * n == 0: RT_OK; a NULL buffer: RT_ERR_INVALID_ARG; no scene written: RT_ERR_STATE.  Otherwise the contract of rt_trace_rays
+ * above applies word for word: a query sees every write made before it, takes no slot of the event ring, changes no field of
+ * rt_stats, has no rt_kernel_id, is unaffected by mode and variant, never disturbs frames in flight, and queries run in call order. */
+int rt_trace_rays_multi(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, uint32_t k, rt_hit* hits, void* hip_stream);  /* device, async */
+int rt_trace_rays_multi_host(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, uint32_t k, rt_hit* hits);               /* host, sync   */
+
 /* ---- shaded ray queries: the renderer's colour along rays the host supplies (RK:101-144, optionally RK:91-96) -------------- */
 
 typedef struct rt_shade { float r, g, b, dist; } rt_shade;      /* 16 bytes */

@@ -11,6 +11,7 @@ runs REPS times through the device path on one stream, once per kind: "nearest" 
 kernels, and the line printed here gives the same from hipEvents around the batch.  The frame's
 figure is rt_stats.rays / kernel_ms of an awaited frame (RK:114 + RK:153 traversals, reflections and shadow rays included).
 "shade" is rt_shade_rays on the same rays (whole paths: rays_per_ms counts caller rays, not traversals; hit_fraction: dist > 0).
+"multi1" / "multi4" / "multi8" is rt_trace_rays_multi with k = 1, 4, 8 under the same limits (hit_fraction: hit 0 exists).
 "shade_vs_frame": the 2^20 primary rays of a 1024 x 1024 frame shaded with RT_SHADE_COMPOSE, beside kernel_ms of that frame
 through rt_render -- the same pixels by both routes -- on the reference's scene and on C3's spheres (the query searches the
 spheres by brute force, the frame walks the hierarchy)."""
@@ -62,6 +63,10 @@ def timed_one(torch, r, rays, kind):
     elif kind == "shade":
         out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
         run = lambda: r.shade_rays(rays, out=out)
+    elif kind.startswith("multi"):
+        k = int(kind[5:])
+        out = torch.empty((rays.shape[0], k, 8), dtype=torch.float32, device=rays.device)
+        run = lambda: r.trace_rays_multi(rays, k=k, limits=True, out=out)
     else:
         out = torch.empty_like(rays)
         run = lambda: r.trace_rays(rays, out=out, limits=kind == "limited")
@@ -78,6 +83,8 @@ def timed_one(torch, r, rays, kind):
         hits = int((out > 0).sum().item())
     elif kind == "shade":
         hits = int((out[:, 3] > 0).sum().item())
+    elif kind.startswith("multi"):
+        hits = int((out[:, 0, 3].view(torch.int32) >= 0).sum().item())
     else:
         hits = int((out[:, 3].view(torch.int32) >= 0).sum().item())
     return {"ms": round(ms, 4), "rays_per_ms": round(rays.shape[0] / ms), "hit_fraction": round(hits / rays.shape[0], 3)}
@@ -85,7 +92,7 @@ def timed_one(torch, r, rays, kind):
 
 def timed(torch, r, rays):
     res = {"rays": int(rays.shape[0])}
-    for kind in ("nearest", "limited", "occluded", "shade"):
+    for kind in ("nearest", "limited", "occluded", "shade", "multi1", "multi4", "multi8"):
         res[kind] = timed_one(torch, r, rays, kind)
     return res
 
