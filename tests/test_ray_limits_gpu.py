@@ -10,8 +10,9 @@ import compute_raytracer_amd as rt
 from compute_raytracer_amd import abi, load_mesh
 from compute_raytracer_amd.procedural import obj_floor
 from helpers import tri_buffers, triangle_scene
-from test_ray_query_gpu import (bits, camera_rays, check_triangle_hits, cross, dot, make_renderer, mat_apply, random_rays,
-                                restate_triangle_hits, same, scene_box, sphere_scene_with_duplicates, tri_cases)
+from query_common import (brute_triangles, camera_rays, check_triangle_hits, pack, random_rays, restate_triangle_hits, same,
+                          scene_box, trace_spheres)
+from test_ray_query_gpu import make_renderer, sphere_scene_with_duplicates, tri_cases
 
 pytestmark = pytest.mark.gpu
 F = np.float32
@@ -84,13 +85,6 @@ def quad_stack(k, instanced):
 
 
 # ---- rays and queries ---------------------------------------------------------------------------------------------------------
-def pack(o, d, tmin=0.001, tmax=9999.0):
-    rays = np.zeros((o.shape[0], 8), F)
-    rays[:, 0:3], rays[:, 4:7] = o, d
-    rays[:, 3], rays[:, 7] = tmin, tmax
-    return rays
-
-
 def host_ex(r, rays, flags):
     hits = np.zeros(rays.shape[0], dtype=abi.HIT_DTYPE)
     abi.check(r._lib.rt_trace_rays_host_ex(r._ctx, rays.ctypes.data, rays.shape[0], flags, hits.ctypes.data), r._ctx)
@@ -125,80 +119,6 @@ def check_occlusion(r, o, d, tmin, tmax):
         (occ.astype(bool) != (near["prim"] >= 0)).sum())
     assert np.array_equal(r.occluded(o, d, tmin, tmax), occ.astype(bool))
     return int(occ.sum())
-
-
-# ---- triangles: the float32 brute force ---------------------------------------------------------------------------------------
-def blas_slots(buf, root):
-    """The lookup slots of the leaves under node `root` (RK:246-332 reaches no others)."""
-    nodes = np.asarray(buf["nodes"], F)
-    n_lookup = len(buf["tri_lookup"])
-    out, todo = [], [int(root)]
-    while todo:
-        i = min(todo.pop(), nodes.shape[0] - 1)
-        left, count = int(nodes[i, 3]), int(nodes[i, 7])
-        if count == 0:
-            todo += [left, left + 1]
-        else:
-            out += [min(left + k, n_lookup - 1) for k in range(count)]
-    return np.unique(np.asarray(out, np.int64))
-
-
-def brute_triangles(buf, o, d, tmin, tmax):
-    """The smallest t that hit_triangle (RK:344-381) accepts within (tmin, tmax) over every (triangle, instance) pair, in the
-    same float32 operations; +inf where none does."""
-    blas = np.asarray(buf["blas"], F).reshape(-1, 20)
-    tris = np.asarray(buf["triangles"], F).reshape(-1, 40)
-    lookup = np.asarray(buf["tri_lookup"], F)
-    n = o.shape[0]
-    best = np.full(n, np.inf, F)
-    tmin = np.broadcast_to(np.asarray(tmin, F), (n,))
-    tmax = np.broadcast_to(np.asarray(tmax, F), (n,))
-    for bi in np.unique(np.asarray(buf["blas_lookup"], np.int64).clip(0, blas.shape[0] - 1)):
-        m = np.broadcast_to(blas[bi], (n, 20))
-        oo, od = mat_apply(m, o, 1.0), mat_apply(m, d, 0.0)
-        prims = np.minimum(lookup[blas_slots(buf, blas[bi, 16])].astype(np.int64), tris.shape[0] - 1)
-        A, B, C = tris[prims, 0:3], tris[prims, 12:15], tris[prims, 24:27]
-        e1, e2 = (B - A)[None], (C - A)[None]
-        for s0 in range(0, n, 256):
-            sl = slice(s0, s0 + 256)
-            odc, ooc = od[sl, None, :], oo[sl, None, :]
-            rce2 = cross(np.broadcast_to(odc, (odc.shape[0],) + e2.shape[1:]), np.broadcast_to(e2, (odc.shape[0],) + e2.shape[1:]))
-            det = dot(e1, rce2)
-            s = ooc - A[None]
-            u = dot(s, rce2)
-            sce1 = cross(s, np.broadcast_to(e1, s.shape))
-            v = dot(np.broadcast_to(odc, s.shape), sce1)
-            t = (F(1.0) / det) * dot(np.broadcast_to(e2, s.shape), sce1)
-            ok = ~(det < F(0.00001)) & ~((u < 0) | (u > det)) & ~((v < 0) | (u + v > det))
-            ok &= (t > tmin[sl, None]) & (t < tmax[sl, None])
-            cand = np.where(ok, t, np.inf).min(axis=1)
-            best[sl] = np.minimum(best[sl], cand)
-    return best
-
-
-# ---- spheres: rt_oracle_np._trace with per-ray limits ---------------------------------------------------------------------------
-def trace_spheres(sp, o, d, tmin, tmax):
-    """RK:311-322 over the spheres with hitSphere (HK:307-331) in float32, tMin = tmin, the running nearest starting at tmax."""
-    n = o.shape[0]
-    ox, oy, oz, dx, dy, dz = (o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2])
-    def _dot(ax, ay, az, bx, by, bz):
-        return (ax * bx + ay * by) + az * bz
-    nearest = np.broadcast_to(np.asarray(tmax, F), (n,)).copy()
-    tmin = np.broadcast_to(np.asarray(tmin, F), (n,))
-    idx = np.full(n, -1, np.int64)
-    a = _dot(dx, dy, dz, dx, dy, dz)
-    for i in range(sp.shape[0]):
-        cx, cy, cz, radius = sp[i, 0], sp[i, 1], sp[i, 2], sp[i, 7]
-        ocx, ocy, ocz = ox - cx, oy - cy, oz - cz
-        b = F(2.0) * _dot(dx, dy, dz, ocx, ocy, ocz)
-        c = _dot(ocx, ocy, ocz, ocx, ocy, ocz) - radius * radius
-        disc = b * b - F(4.0) * a * c
-        with np.errstate(invalid="ignore"):
-            t = (-b - np.sqrt(disc)) / (F(2.0) * a)
-            hit = (disc > 0) & (t > tmin) & (t < nearest)
-        nearest = np.where(hit, t, nearest)
-        idx = np.where(hit, i, idx)
-    return nearest, idx
 
 
 def sphere_setup(n):

@@ -10,26 +10,16 @@ import compute_raytracer_amd as rt
 from compute_raytracer_amd import abi, load_mesh
 from compute_raytracer_amd.procedural import obj_floor
 from helpers import tri_buffers, triangle_scene
-from test_ray_limits_gpu import (FORMS, NOT_EXHAUSTIVE, blas_slots, host_ex, host_occ, pack, quad_stack, same_records, sphere_rays,
-                                 sphere_setup)
-from test_ray_query_gpu import (camera_rays, cross, dot, make_renderer, mat_apply, random_rays, restate_triangle_hits, same,
-                                scene_box)
+from query_common import (MISS, all_triangle_hits, brute_spheres, camera_rays, check_order, host_multi, k_smallest, pack, random_rays,
+                          restate_triangle_hits, same, scene_box)
+from test_ray_limits_gpu import FORMS, NOT_EXHAUSTIVE, host_ex, host_occ, quad_stack, same_records, sphere_rays, sphere_setup
+from test_ray_query_gpu import make_renderer
 
 pytestmark = pytest.mark.gpu
 F = np.float32
 L = abi.RT_QUERY_LIMITS
-MISS = np.zeros(1, dtype=abi.HIT_DTYPE)
-MISS["t"], MISS["prim"], MISS["instance"] = -1.0, -1, -1
 # forms of at least thirteen instances in front of the camera: among 4,000 rays some cross three surfaces, some more than four
 DENSE = ("inst13", "inst17", "inst17_u16", "inst17_u32")
-
-
-def host_multi(r, rays, flags, k):
-    """rt_trace_rays_multi_host into a buffer of junk: (n, k) records, every one of them written."""
-    hits = np.zeros((rays.shape[0], k), dtype=abi.HIT_DTYPE)
-    hits.view(np.uint8)[...] = 0x5A
-    abi.check(r._lib.rt_trace_rays_multi_host(r._ctx, rays.ctypes.data, rays.shape[0], flags, k, hits.ctypes.data), r._ctx)
-    return hits
 
 
 def check_layout(h):
@@ -41,19 +31,6 @@ def check_layout(h):
     return count
 
 
-def check_order(h, tmin, tmax):
-    """Strictly ascending (t, instance, prim) -- hence distinct -- and tmin < t < tmax."""
-    filled = h["prim"] >= 0
-    a, b = h[:, :-1], h[:, 1:]
-    both = filled[:, 1:]
-    before = (a["t"] < b["t"]) | ((a["t"] == b["t"]) & ((a["instance"] < b["instance"]) |
-                                                      ((a["instance"] == b["instance"]) & (a["prim"] < b["prim"]))))
-    assert np.all(before[both]), "records out of order or repeated on %d rays" % int((~before & both).any(axis=1).sum())
-    lo = np.broadcast_to(np.asarray(tmin, F).reshape(-1, 1), h.shape)
-    hi = np.broadcast_to(np.asarray(tmax, F).reshape(-1, 1), h.shape)
-    assert np.all(h["t"][filled] > lo[filled]) and np.all(h["t"][filled] < hi[filled])
-
-
 def check_restated(buf, o, d, h):
     """t, u, v and the normal of every filled record are the float32 restatement's for its (prim, instance)."""
     ray, j = np.nonzero(h["prim"] >= 0)
@@ -63,87 +40,11 @@ def check_restated(buf, o, d, h):
     assert same(t, g["t"]) and same(u, g["u"]) and same(v, g["v"]) and same(nrm, g["normal"])
 
 
-# ---- triangles: the float32 brute force ---------------------------------------------------------------------------------------
-def all_triangle_hits(buf, o, d):
-    """Every (ray, t, instance, prim) that passes hit_triangle's tests (RK:344-379) over every (triangle, instance) pair, in the
-    same float32 operations as brute_triangles; the limits are applied by k_smallest."""
-    blas = np.asarray(buf["blas"], F).reshape(-1, 20)
-    tris = np.asarray(buf["triangles"], F).reshape(-1, 40)
-    lookup = np.asarray(buf["tri_lookup"], F)
-    n = o.shape[0]
-    out = []
-    for bi in np.unique(np.asarray(buf["blas_lookup"], np.int64).clip(0, blas.shape[0] - 1)):
-        m = np.broadcast_to(blas[bi], (n, 20))
-        oo, od = mat_apply(m, o, 1.0), mat_apply(m, d, 0.0)
-        prims = np.unique(np.minimum(lookup[blas_slots(buf, blas[bi, 16])].astype(np.int64), tris.shape[0] - 1))
-        A, B, C = tris[prims, 0:3], tris[prims, 12:15], tris[prims, 24:27]
-        e1, e2 = (B - A)[None], (C - A)[None]
-        for s0 in range(0, n, 256):
-            odc, ooc = od[s0:s0 + 256, None, :], oo[s0:s0 + 256, None, :]
-            shape = (odc.shape[0],) + e2.shape[1:]
-            rce2 = cross(np.broadcast_to(odc, shape), np.broadcast_to(e2, shape))
-            det = dot(e1, rce2)
-            s = ooc - A[None]
-            u = dot(s, rce2)
-            sce1 = cross(s, np.broadcast_to(e1, s.shape))
-            v = dot(np.broadcast_to(odc, s.shape), sce1)
-            t = (F(1.0) / det) * dot(np.broadcast_to(e2, s.shape), sce1)
-            ok = ~(det < F(0.00001)) & ~((u < 0) | (u > det)) & ~((v < 0) | (u + v > det))
-            ray, tri = np.nonzero(ok)
-            out.append((ray + s0, t[ray, tri], np.full(ray.size, bi), prims[tri]))
-    return tuple(np.concatenate(c) for c in zip(*out))
-
-
-def k_smallest(n, k, cand, tmin, tmax):
-    """Per ray the k smallest (t, instance, prim) among `cand` with tmin < t < tmax: (n, k) t / instance / prim (-1 where there
-    are fewer), and the number of accepted hits per ray before the cut."""
-    ray, t, inst, prim = cand
-    tmin = np.broadcast_to(np.asarray(tmin, F), (n,))
-    tmax = np.broadcast_to(np.asarray(tmax, F), (n,))
-    keep = (t > tmin[ray]) & (t < tmax[ray])
-    ray, t, inst, prim = ray[keep], t[keep], inst[keep], prim[keep]
-    order = np.lexsort((prim, inst, t, ray))
-    ray, t, inst, prim = ray[order], t[order], inst[order], prim[order]
-    total = np.bincount(ray, minlength=n)
-    rank = np.arange(ray.size) - (np.cumsum(total) - total)[ray]
-    cut = rank < k
-    T, I, P = np.full((n, k), -1.0, F), np.full((n, k), -1, np.int32), np.full((n, k), -1, np.int32)
-    T[ray[cut], rank[cut]], I[ray[cut], rank[cut]], P[ray[cut], rank[cut]] = t[cut], inst[cut], prim[cut]
-    return T, I, P, total
-
-
 def check_against_brute(h, want):
     T, I, P, _ = want
     bad = (h["prim"] != P) | (h["instance"] != I) | (h["t"].view(np.uint32) != T.view(np.uint32))
     assert not bad.any(), "the walk and the brute force differ on %d rays, first %s" % (
         int(bad.any(axis=1).sum()), np.nonzero(bad.any(axis=1))[0][:5])
-
-
-# ---- spheres: every sphere's near root, no running nearest --------------------------------------------------------------------
-def brute_spheres(sp, o, d, tmin, tmax, k):
-    """trace_spheres' per-sphere t (HK:308-317) in float32; accepted: disc > 0 and tmin < t < tmax; the k smallest (t, index)."""
-    n = o.shape[0]
-    ox, oy, oz, dx, dy, dz = (c[:, None] for c in (o[:, 0], o[:, 1], o[:, 2], d[:, 0], d[:, 1], d[:, 2]))
-    def _dot(ax, ay, az, bx, by, bz):
-        return (ax * bx + ay * by) + az * bz
-    tmin = np.broadcast_to(np.asarray(tmin, F), (n,))[:, None]
-    tmax = np.broadcast_to(np.asarray(tmax, F), (n,))[:, None]
-    a = _dot(dx, dy, dz, dx, dy, dz)
-    cx, cy, cz, radius = sp[None, :, 0], sp[None, :, 1], sp[None, :, 2], sp[None, :, 7]
-    ocx, ocy, ocz = ox - cx, oy - cy, oz - cz
-    b = F(2.0) * _dot(dx, dy, dz, ocx, ocy, ocz)
-    c = _dot(ocx, ocy, ocz, ocx, ocy, ocz) - radius * radius
-    disc = b * b - F(4.0) * a * c
-    with np.errstate(invalid="ignore", divide="ignore"):
-        t = (-b - np.sqrt(disc)) / (F(2.0) * a)
-        hit = (disc > 0) & (t > tmin) & (t < tmax)
-    key = np.where(hit, t, F(np.inf))
-    idx = np.argsort(key, axis=1, kind="stable")[:, :k]            # (stable: the lower index first on equal t)
-    if idx.shape[1] < k:
-        idx = np.concatenate([idx, np.zeros((n, k - idx.shape[1]), idx.dtype)], axis=1)
-    rows = np.arange(n)[:, None]
-    found = hit[rows, idx] & (np.arange(k)[None, :] < sp.shape[0])
-    return np.where(found, t[rows, idx], F(-1.0)).astype(F), np.where(found, idx, -1).astype(np.int32)
 
 
 # ---- 1. layers ----------------------------------------------------------------------------------------------------------------

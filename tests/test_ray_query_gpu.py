@@ -10,124 +10,16 @@ import compute_raytracer_amd as rt
 from compute_raytracer_amd import abi
 from helpers import deepen_top_level, leafy_scene, ref_fixture, spine_scene, tri_buffers, triangle_scene
 from oracle import rt_oracle_np
+from query_common import axis_rays, camera_rays, check_triangle_hits, random_rays, same, scene_box
 
 pytestmark = pytest.mark.gpu
 F = np.float32
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
 
 
 def make_renderer(scene, mat=None, W=96, H=64, sky=None):
     r = rt.RendererRaytracing(W, H, scene, maxBounces=2).initialize(sky, mat)
     r.recalculateScene()
     return r
-
-
-# ---- rays --------------------------------------------------------------------------------------------------------------------
-def camera_rays(scene, W, H, step=1):
-    """The primary rays of a W x H frame (RK:76-86 in float32, the oracle's order), every `step`-th pixel."""
-    p = scene.pack_params(2)
-    cam, fw, rgt, up = p[0:3], p[4:7], p[8:11], p[12:15]
-    ys, xs = np.mgrid[0:H:step, 0:W:step]
-    xs = xs.reshape(-1); ys = ys.reshape(-1)
-    hc = (xs.astype(F) - F(W) / F(2)) / F(W) * F(2)
-    vc = (F(H) / F(2) - ys.astype(F)) / F(W) * F(2)
-    d = np.stack([(fw[k] + hc * rgt[k]) + vc * up[k] for k in range(3)], axis=1).astype(F)
-    ln = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
-    d = d / ln[:, None]
-    return np.broadcast_to(cam, d.shape).astype(F), d.astype(F)
-
-
-def random_rays(lo, hi, n, seed):
-    """Incoherent rays: origins in the box grown by half its size on every side (inside and outside the scene), directions of
-    lengths 0.05 .. 20 (not unit)."""
-    rng = np.random.default_rng(seed)
-    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
-    ext = hi - lo
-    o = rng.uniform(lo - 0.5 * ext, hi + 0.5 * ext, (n, 3)).astype(F)
-    d = rng.normal(size=(n, 3))
-    d = d / np.linalg.norm(d, axis=1)[:, None] * rng.uniform(0.05, 20.0, (n, 1))
-    return o, d.astype(F)
-
-
-def axis_rays(lo, hi, seed, per_axis=100):
-    """Directions along the axes (the inverse direction is +-inf in two components)."""
-    rng = np.random.default_rng(seed)
-    o = rng.uniform(lo, hi, (6 * per_axis, 3)).astype(F)
-    d = np.zeros((6 * per_axis, 3), F)
-    for k in range(6):
-        d[k * per_axis:(k + 1) * per_axis, k // 2] = F(1.0 if k % 2 == 0 else -1.0) * F(0.5 + k)
-    return o, d
-
-
-def scene_box(buf, scene):
-    """The top-level root's box, within 20 of the camera (the reference's floor spans millions)."""
-    root, cam = buf["nodes"][0], scene.pack_params(2)[0:3]
-    return np.maximum(root[0:3], cam - 20.0), np.minimum(root[4:7], cam + 20.0)
-
-
-# ---- the triangle hit restated in float32 --------------------------------------------------------------------------------------
-def dot(a, b):
-    return (a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1]) + a[..., 2] * b[..., 2]
-
-
-def cross(a, b):
-    return np.stack([a[..., 1] * b[..., 2] - b[..., 1] * a[..., 2], a[..., 2] * b[..., 0] - b[..., 2] * a[..., 0],
-                     a[..., 0] * b[..., 1] - b[..., 0] * a[..., 1]], axis=-1)
-
-
-def mat_apply(m, v, w):
-    """mat4 (column-major, m[4c + r]) * vec4(v, w), summed over columns left to right (RK:254-255)."""
-    return np.stack([((m[:, r] * v[:, 0] + m[:, 4 + r] * v[:, 1]) + m[:, 8 + r] * v[:, 2]) + m[:, 12 + r] * F(w) for r in range(3)], axis=1)
-
-
-def restate_triangle_hits(buf, o, d, prim, inst):
-    """t, u, v (RK:354-379) of triangle `prim` in the object space of instance `inst`, and the shading normal (RK:381-382,
-    RK:334-338): every operation a float32 operation, in the oracle's order."""
-    m = np.asarray(buf["blas"], F).reshape(-1, 20)[inst]
-    tri = np.asarray(buf["triangles"], F).reshape(-1, 40)[prim]
-    oo, od = mat_apply(m, o, 1.0), mat_apply(m, d, 0.0)
-    A, B, C = tri[:, 0:3], tri[:, 12:15], tri[:, 24:27]
-    e1, e2 = B - A, C - A
-    rce2 = cross(od, e2)
-    det = dot(e1, rce2)
-    s = oo - A
-    u = dot(s, rce2)
-    sce1 = cross(s, e1)
-    v = dot(od, sce1)
-    inv = F(1.0) / det
-    t = inv * dot(e2, sce1)
-    u = u * inv
-    v = v * inv
-    w = (F(1.0) - u) - v
-    n = (w[:, None] * tri[:, 4:7] + u[:, None] * tri[:, 16:19]) + v[:, None] * tri[:, 28:31]
-    tn = np.stack([((m[:, 4 * r + 0] * n[:, 0] + m[:, 4 * r + 1] * n[:, 1]) + m[:, 4 * r + 2] * n[:, 2]) + m[:, 4 * r + 3] * F(0.0)
-                   for r in range(3)], axis=1)
-    nrm = tn / np.sqrt(dot(tn, tn))[:, None]
-    return t, u, v, nrm
-
-
-def check_triangle_hits(oracle, buf, o, d, h):
-    t_ref = oracle.trace_tri_rays(buf, o, d)
-    miss = h["prim"] < 0
-    assert np.array_equal(miss, t_ref == F(-1.0)), "miss sets differ: %d vs %d" % (miss.sum(), (t_ref == -1).sum())
-    assert same(h["t"], t_ref), "t differs from the oracle on %d rays" % int((bits(h["t"]) != bits(t_ref)).sum())
-    assert np.all(h["instance"][miss] == -1) and np.all(h["u"][miss] == 0) and np.all(h["v"][miss] == 0)
-    assert np.all(h["normal"][miss] == 0)
-    hit = ~miss
-    if hit.any():
-        assert np.all(h["instance"][hit] >= 0) and np.all(h["prim"][hit] < len(buf["triangles"]))
-        with np.errstate(all="ignore"):
-            t, u, v, nrm = restate_triangle_hits(buf, o[hit], d[hit], h["prim"][hit], h["instance"][hit])
-        assert same(t, h["t"][hit]) and same(u, h["u"][hit]) and same(v, h["v"][hit])
-        assert same(nrm, h["normal"][hit])
-    return int(hit.sum())
 
 
 def tri_cases():
