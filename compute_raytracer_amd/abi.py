@@ -24,6 +24,7 @@ RT_MODE_STRICT = 1
 RT_QUERY_LIMITS = 1      # flags of rt_trace_rays_ex / rt_occluded: ray words 3 and 7 are tmin and tmax
 RT355_MAX_HITS = 8       # the largest k of rt_trace_rays_multi
 RT_SHADE_COMPOSE = 1     # flags of rt_shade_rays: r, g, b is pixelColor (RK:91-96) instead of rayColor
+RT355_MAX_SUPERSAMPLE = 4   # the largest s of rt_render_samples
 
 # every symbol include/rt355.h declares (tests check the library exports each of them)
 SYMBOLS = [
@@ -42,6 +43,7 @@ SYMBOLS = [
     "rt_build_hierarchy_ex",
     "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_rays_multi", "rt_trace_rays_multi_host",
+    "rt_render_samples", "rt_render_samples_host",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -190,6 +192,8 @@ def load():
         "rt_shade_rays_host": (ctypes.c_int, [vp, vp, u32, u32, vp]),
         "rt_trace_rays_multi": (ctypes.c_int, [vp, vp, u32, u32, u32, vp, vp]),
         "rt_trace_rays_multi_host": (ctypes.c_int, [vp, vp, u32, u32, u32, vp]),
+        "rt_render_samples": (ctypes.c_int, [vp, u32, vp, sz, vp, sz, vp]),
+        "rt_render_samples_host": (ctypes.c_int, [vp, u32, vp, sz, vp, sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

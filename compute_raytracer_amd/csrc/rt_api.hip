@@ -1415,14 +1415,10 @@ int rt_filter_plan(const float* records, uint32_t n, const float params[24], int
 
 // ---- ray queries (rt_query.hip) ------------------------------------------------------------------------------------------
 
-// What a query on `s` reads, and its order behind the last scene update.  Triangle scenes: `ts`, with the instance data in the
-// arguments (*inst = 1) when it travels with the frames -- the per-frame buffers then hold an older pose -- and otherwise from a
-// version of the per-frame buffers that holds the current state (every version, for instance sets written by write_versions).
-static int query_prepare(rt_ctx* c, const char* who, hipStream_t s, bool& tri, RtTriScene& ts, int& inst) {
+// Is there a scene for a query to read?  (query_prepare's first check; rt_render_samples asks before it looks at capacities)
+static int query_scene_written(rt_ctx* c, const char* who) {
     char msg[160];
-    tri = c->scene_kind == 1;
-    inst = 0;
-    if (tri) {
+    if (c->scene_kind == 1) {
         const bool have_blas = c->inst.blas_on ? !c->inst.blas.empty() : c->d_blas[0].used != 0;
         const bool have_lookup = c->inst.lookup_on ? !c->inst.lookup.empty() : c->d_blas_lookup[0].used != 0;
         if (!c->d_tri.used || !c->nodes_used || !have_blas || !c->d_tri_lookup.used || !have_lookup) {
@@ -1433,6 +1429,15 @@ static int query_prepare(rt_ctx* c, const char* who, hipStream_t s, bool& tri, R
         std::snprintf(msg, sizeof msg, "%s: no scene has been written", who);
         return fail(RT_ERR_STATE, msg);
     }
+    return RT_OK;
+}
+// What a query on `s` reads, and its order behind the last scene update.  Triangle scenes: `ts`, with the instance data in the
+// arguments (*inst = 1) when it travels with the frames -- the per-frame buffers then hold an older pose -- and otherwise from a
+// version of the per-frame buffers that holds the current state (every version, for instance sets written by write_versions).
+static int query_prepare(rt_ctx* c, const char* who, hipStream_t s, bool& tri, RtTriScene& ts, int& inst) {
+    { int rc = query_scene_written(c, who); if (rc != RT_OK) return rc; }
+    tri = c->scene_kind == 1;
+    inst = 0;
     RT_HIP(hipSetDevice(c->device));
     if (!c->ev_query) RT_HIP(hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
     if (tri) { int rc = ensure_corners(c, s); if (rc != RT_OK) return rc; }
@@ -1673,8 +1678,21 @@ int rt_pick(rt_ctx* c, const uint32_t* xy, uint32_t n, rt_hit* hits) {
 
 static_assert(sizeof(rt_shade) == 16, "rt_shade is one float4");
 
-// The argument checks of both forms, in query_device's order: flags, context, n == 0 (*done), pointers; then the state a shade
-// query reads beside the scene -- the parameters and the sky -- and the mesh texture a frame would default.
+// The state a shade query reads beside the scene -- the parameters and the sky -- and the mesh texture a frame would default
+static int shade_state(const char* who, rt_ctx* c) {
+    char msg[160];
+    if (!c->have_params) { std::snprintf(msg, sizeof msg, "%s: rt_write_params has not been called", who); return fail(RT_ERR_STATE, msg); }
+    for (int i = 0; i < 6; ++i)
+        if (!c->d_face[i]) { std::snprintf(msg, sizeof msg, "%s: all six cube map faces must be written first", who); return fail(RT_ERR_STATE, msg); }
+    if (c->scene_kind == 1 && c->d_tri.used && !c->d_tex.used) {   // meshTex is mandatory in the reference (RR:113-114); default: 1x1 white
+        const uint8_t white[4] = {255, 255, 255, 255};
+        int rc = rt_write_mesh_texture(c, 1, 1, white);
+        if (rc != RT_OK) return rc;
+    }
+    return RT_OK;
+}
+
+// The argument checks of both forms, in query_device's order: flags, context, n == 0 (*done), pointers; then shade_state.
 static int shade_check(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, const rt_shade* out, bool device, bool& done) {
     char msg[160];
     done = false;
@@ -1687,21 +1705,12 @@ static int shade_check(const char* who, rt_ctx* c, const float* rays, uint32_t n
         std::snprintf(msg, sizeof msg, "%s: rays and out must be 16-byte aligned", who);
         return fail(RT_ERR_INVALID_ARG, msg);
     }
-    if (!c->have_params) { std::snprintf(msg, sizeof msg, "%s: rt_write_params has not been called", who); return fail(RT_ERR_STATE, msg); }
-    for (int i = 0; i < 6; ++i)
-        if (!c->d_face[i]) { std::snprintf(msg, sizeof msg, "%s: all six cube map faces must be written first", who); return fail(RT_ERR_STATE, msg); }
-    if (c->scene_kind == 1 && c->d_tri.used && !c->d_tex.used) {   // meshTex is mandatory in the reference (RR:113-114); default: 1x1 white
-        const uint8_t white[4] = {255, 255, 255, 255};
-        int rc = rt_write_mesh_texture(c, 1, 1, white);
-        if (rc != RT_OK) return rc;
-    }
-    return RT_OK;
+    return shade_state(who, c);
 }
 
 // The shade kernel on `s` behind query_prepare: parameters, cube faces and sky flags as rt_enqueue assembles them for a frame,
 // by value in the kernel's arguments -- no slot of the event ring, no counters, no field of the stats.
-static int shade_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flags, float4* out, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
-    RtFrameArgs fa;
+static void shade_frame_args(const rt_ctx* c, RtFrameArgs& fa) {
     std::memset(&fa, 0, sizeof fa);
     std::memcpy(fa.p, c->params, sizeof fa.p);
     fa.sky_flat = 1u;           // six 1x1 faces of one colour
@@ -1711,6 +1720,10 @@ static int shade_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flag
         if (c->fw[i] != 1u || c->fh[i] != 1u || c->face_texel0[i] != c->face_texel0[0]) fa.sky_flat = 0u;
         if (c->fw[i] != c->fw[0] || c->fh[i] != c->fw[0]) fa.sky_seamless = 0u;
     }
+}
+static int shade_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flags, float4* out, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+    RtFrameArgs fa;
+    shade_frame_args(c, fa);
     if (tri) RT_HIP(rt_launch_shade_triangles(fa, ts, inst, rays, flags, out, n, s));
     else RT_HIP(rt_launch_shade_spheres(fa, c->d_records, c->n, rays, flags, out, n, s));
     RT_HIP(hipEventRecord(c->ev_query, s));
@@ -1745,6 +1758,77 @@ int rt_shade_rays_host(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags,
     RT_HIP(hipMemcpyAsync(c->d_qrays.p, rays, bytes, hipMemcpyHostToDevice, s));
     { int rc = shade_launch(c, static_cast<const float4*>(c->d_qrays.p), n, flags, static_cast<float4*>(c->d_qhits.p), s, tri, ts, inst); if (rc != RT_OK) return rc; }
     RT_HIP(hipMemcpyAsync(out, c->d_qhits.p, out_bytes, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    return RT_OK;
+}
+
+// ---- supersampled frames (rt_sample.hip) ---------------------------------------------------------------------------------------
+
+// The checks of both forms, in the header's order: s, context, outputs; the state (rt_resize, a scene, shade_state); capacities
+static int sample_check(const char* who, rt_ctx* c, uint32_t s, const uint8_t* rgba8, size_t cap8, const float* rgbaf, size_t capf, bool device) {
+    char msg[160];
+    if (s == 0u || s > RT355_MAX_SUPERSAMPLE) {
+        std::snprintf(msg, sizeof msg, "%s: s = %u is outside 1 .. RT355_MAX_SUPERSAMPLE (%u)", who, s, RT355_MAX_SUPERSAMPLE);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!rgba8 && !rgbaf) { std::snprintf(msg, sizeof msg, "%s: both outputs are NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (device && (reinterpret_cast<uintptr_t>(rgba8) % 4u || reinterpret_cast<uintptr_t>(rgbaf) % 16u)) {
+        std::snprintf(msg, sizeof msg, "%s: rgba8 must be 4-byte and rgbaf 16-byte aligned", who);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    if (!c->W || !c->H) { std::snprintf(msg, sizeof msg, "%s: rt_resize has not been called", who); return fail(RT_ERR_STATE, msg); }
+    { int rc = query_scene_written(c, who); if (rc != RT_OK) return rc; }
+    { int rc = shade_state(who, c); if (rc != RT_OK) return rc; }
+    const size_t px = (size_t)c->W * c->H;
+    if ((rgba8 && cap8 < px * 4u) || (rgbaf && capf < px * 16u)) {
+        std::snprintf(msg, sizeof msg, "%s: a %u x %u frame needs %zu bytes of rgba8 and %zu of rgbaf", who, c->W, c->H, px * 4u, px * 16u);
+        return fail(RT_ERR_CAPACITY, msg);
+    }
+    return RT_OK;
+}
+
+// The sample kernel on `s` behind query_prepare: shade_launch's arguments with the camera of the last rt_write_params and the
+// target the samples are pixels of, s W x s H -- the whole frame, whatever the partition
+static int sample_launch(rt_ctx* c, uint32_t ss, uint8_t* rgba8, float* rgbaf, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+    RtFrameArgs fa;
+    shade_frame_args(c, fa);
+    fa.W = ss * c->W; fa.H = ss * c->H;
+    const RtSampleOut o = {c->W, c->H, ss, reinterpret_cast<uint32_t*>(rgba8), reinterpret_cast<float4*>(rgbaf)};
+    if (tri) RT_HIP(rt_launch_sample_triangles(fa, ts, inst, o, s));
+    else RT_HIP(rt_launch_sample_spheres(fa, c->d_records, c->n, o, s));
+    RT_HIP(hipEventRecord(c->ev_query, s));
+    c->query_pending = true;
+    c->query_last = s;
+    return RT_OK;
+}
+
+int rt_render_samples(rt_ctx* c, uint32_t ss, uint8_t* rgba8, size_t cap8, float* rgbaf, size_t capf, void* hip_stream) {
+    { int rc = sample_check("rt_render_samples", c, ss, rgba8, cap8, rgbaf, capf, true); if (rc != RT_OK) return rc; }
+    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_render_samples", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    return sample_launch(c, ss, rgba8, rgbaf, s, tri, ts, inst);
+}
+
+int rt_render_samples_host(rt_ctx* c, uint32_t ss, uint8_t* rgba8, size_t cap8, float* rgbaf, size_t capf) {
+    { int rc = sample_check("rt_render_samples_host", c, ss, rgba8, cap8, rgbaf, capf, false); if (rc != RT_OK) return rc; }
+    hipStream_t s;
+    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_render_samples_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    // (the staging buffers of the ray queries, idle between calls: the bytes where their rays go, the floats where their results go)
+    const size_t px = (size_t)c->W * c->H;
+    if (rgba8) { int rc = grow_staging(c->d_qrays, px * 4u); if (rc != RT_OK) return rc; }
+    if (rgbaf) { int rc = grow_staging(c->d_qhits, px * 16u); if (rc != RT_OK) return rc; }
+    { int rc = sample_launch(c, ss, rgba8 ? static_cast<uint8_t*>(c->d_qrays.p) : nullptr, rgbaf ? static_cast<float*>(c->d_qhits.p) : nullptr, s, tri, ts, inst);
+      if (rc != RT_OK) return rc; }
+    if (rgba8) RT_HIP(hipMemcpyAsync(rgba8, c->d_qrays.p, px * 4u, hipMemcpyDeviceToHost, s));
+    if (rgbaf) RT_HIP(hipMemcpyAsync(rgbaf, c->d_qhits.p, px * 16u, hipMemcpyDeviceToHost, s));
     RT_HIP(hipStreamSynchronize(s));
     return RT_OK;
 }

@@ -77,4 +77,14 @@ hipError_t rt_launch_shade_triangles(const RtFrameArgs& a, const RtTriScene& t, 
                                      uint32_t n, hipStream_t s);
 hipError_t rt_launch_shade_spheres(const RtFrameArgs& a, const float* records, uint32_t n_spheres, const float4* rays, uint32_t flags,
                                    float4* out, uint32_t n, hipStream_t s);
+// Supersampled frames (rt_sample.hip; include/rt355.h: rt_render_samples): the W x H frame at s x s samples per pixel, resolved in the
+// kernel.  `a` as for the shaded queries, with a.W = s W and a.H = s H -- the target whose pixels the samples are -- and the camera
+// words of a.p read; either output may be null, not both.  inst as above.
+struct RtSampleOut {
+    uint32_t W, H, s;
+    uint32_t* rgba8;           // [H][W] rgba8unorm, row 0 at the top
+    float4* rgbaf;             // [H][W] {r, g, b, 1}
+};
+hipError_t rt_launch_sample_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtSampleOut& o, hipStream_t s);
+hipError_t rt_launch_sample_spheres(const RtFrameArgs& a, const float* records, uint32_t n_spheres, const RtSampleOut& o, hipStream_t s);
 hipError_t rt_launch_pick_rays(const RtFrameArgs& a, const uint32_t* xy, float4* rays, uint32_t n, hipStream_t s);   // xy: [n][2] u32

@@ -354,6 +354,60 @@ class RendererRaytracing:
             cur.wait_stream(run)
         return out
 
+    # ---- supersampled frames: s x s camera rays per pixel, resolved on the device (rt_render_samples / rt_render_samples_host) ----
+    def render_samples(self, s=2, float_out=False, out=None):
+        """The whole width x height frame the next render() would show (recalculateScene() first, as shade_rays does), anti-aliased:
+        each pixel the float32 mean of pixelColor (RK:91-96) over s x s primary rays, 1 <= s <= abi.RT355_MAX_SUPERSAMPLE, added in
+        the order sy outer, sx inner on the device; no sample reaches memory.  s = 1 is render()'s frame byte for byte.
+
+        numpy (out=None): an (H, W, 4) uint8 frame, row 0 at the top, and with float_out a pair of it and the (H, W, 4) float32
+        frame {r, g, b, 1} before the rgba8 store, through rt_render_samples_host.  torch: `out` is a contiguous uint8 (H, W, 4)
+        tensor, a float32 (H, W, 4) tensor, or a pair of both on this renderer's device -> `out`, enqueued through
+        rt_render_samples on torch.cuda.current_stream()."""
+        s = int(s)
+        if out is not None:
+            return self._render_samples_torch(s, out)
+        self.recalculateScene()
+        img = np.zeros((self.height, self.width, 4), np.uint8)
+        flt = np.zeros((self.height, self.width, 4), np.float32) if float_out else None
+        abi.check(self._lib.rt_render_samples_host(self._ctx, s, img.ctypes.data, img.nbytes, flt.ctypes.data if float_out else None,
+                                                   flt.nbytes if float_out else 0), self._ctx)
+        return (img, flt) if float_out else img
+
+    def _render_samples_torch(self, s, out):
+        import torch
+        tensors = list(out) if isinstance(out, (tuple, list)) else [out]
+        img = flt = None
+        for t in tensors:
+            if type(t).__module__.split(".")[0] != "torch" or tuple(t.shape) != (self.height, self.width, 4) or not t.is_contiguous():
+                raise ValueError("render_samples: out must be contiguous (H, W, 4) tensors")
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("render_samples: out must live on cuda:%d, this renderer's device" % self.device)
+            if t.dtype == torch.uint8 and img is None:
+                img = t
+            elif t.dtype == torch.float32 and flt is None:
+                flt = t
+            else:
+                raise ValueError("render_samples: out is one uint8 and / or one float32 tensor")
+        if img is None and flt is None:
+            raise ValueError("render_samples: out holds no tensor")
+        self.recalculateScene()
+        dev = (img if img is not None else flt).device
+        cur = torch.cuda.current_stream(dev)
+        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
+        if cur.cuda_stream == 0:
+            if getattr(self, "_query_stream", None) is None:
+                self._query_stream = torch.cuda.Stream(dev)
+            run = self._query_stream
+            run.wait_stream(cur)
+        abi.check(self._lib.rt_render_samples(self._ctx, s, ctypes.c_void_p(img.data_ptr()) if img is not None else None,
+                                              img.numel() if img is not None else 0,
+                                              ctypes.c_void_p(flt.data_ptr()) if flt is not None else None,
+                                              4 * flt.numel() if flt is not None else 0, ctypes.c_void_p(run.cuda_stream)), self._ctx)
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
     def pick(self, x, y):
         """What pixel (x, y) of the next frame sees first: its primary ray's nearest hit (full-frame coordinates, scalars or arrays
         that broadcast).  Triangle scenes add `mesh`, the instance's mesh index (-1 on a miss)."""

@@ -407,6 +407,38 @@ typedef struct rt_shade { float r, g, b, dist; } rt_shade;      /* 16 bytes */
 int rt_shade_rays(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, rt_shade* out, void* hip_stream);   /* device, async */
 int rt_shade_rays_host(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flags, rt_shade* out);                /* host, sync   */
 
+/* ---- supersampled frames: s x s camera rays per pixel, resolved on the device ------------------------------------------------ */
+
+#define RT355_MAX_SUPERSAMPLE 4u   /* the largest s of rt_render_samples */
+
+/* rt_render_samples / rt_render_samples_host: the whole width x height frame of the last rt_resize, anti-aliased -- a frame-shaped
+ * shaded query that makes its own rays, whatever rt_set_partition says (as for rt_pick).  Device form: the outputs in device
+ * memory of this context's GPU, enqueued on `hip_stream` (NULL = the context's stream), returns at once.  Host form: host memory,
+ * synchronous, staged through buffers the context owns.
+ *
+ * Outputs.  rgba8 is [height][width][4] bytes, row 0 at the top, with a frame's alpha byte (255); in the device form 4-byte aligned.
+ * rgbaf is [height][width][4] float {r, g, b, 1.0f}; in the device form 16-byte aligned.  Either may be NULL, not both.  cap8 and
+ * capf are the sizes of the two buffers in bytes (ignored for a NULL output).
+ *
+ * A pixel.  For sy = 0 .. s-1 (outer) and sx = 0 .. s-1 (inner), c[sy s + sx] is pixelColor (RK:91-96, float) along the primary ray
+ * of pixel (x s + sx, y s + sy) of an (s width) x (s height) target: the ray rt_pick would cast were the target that size
+ * (RK:76-86), under the camera of the last rt_write_params, copied at the call.  Per channel acc = c[0]; acc = acc + c[1]; ... in
+ * that order, mean = acc / (float)(s s) -- float32 throughout, one IEEE division, no fused multiply-add.  rgbaf holds mean; rgba8
+ * holds RK:98's rule applied to it (floor(clamp(mean, 0, 1) * 255 + 0.5), NaN -> 0).  s = 1 is byte for byte the frame rt_render
+ * would produce.  No sample is stored anywhere: the s s colours of a pixel are added on the chip.
+ *
+ * Contract.  That of rt_shade_rays, word for word: sees every write made before it, per-frame instance writes that no frame has
+ * carried yet included; takes no slot of the event ring, changes no field of rt_stats, has no rt_kernel_id; is unaffected by
+ * rt_select_kernel, rt_set_mode and rt_set_variant; never disturbs frames in flight; queries run in call order, and scene writes
+ * after one wait for it.  Sphere scenes are searched with the literal loop.
+ *
+ * Checks, in this order: s == 0 or s > RT355_MAX_SUPERSAMPLE, then a NULL context, then both outputs NULL (or, in the device form,
+ * a misaligned one): RT_ERR_INVALID_ARG.  Then RT_ERR_STATE, as for rt_shade_rays: no rt_resize, no scene written, no
+ * rt_write_params, or a cube map face missing.  Then cap8 < width * height * 4 or capf < width * height * 16 for a non-NULL output:
+ * RT_ERR_CAPACITY. */
+int rt_render_samples(rt_ctx* ctx, uint32_t s, uint8_t* rgba8, size_t cap8, float* rgbaf, size_t capf, void* hip_stream);   /* device, async */
+int rt_render_samples_host(rt_ctx* ctx, uint32_t s, uint8_t* rgba8, size_t cap8, float* rgbaf, size_t capf);                /* host, sync    */
+
 /* ---- multi-GPU: render + RCCL gather behind one call (RR:434-470 across a group of GPUs) ------ */
 
 /* One process per GPU.  Rank 0 calls rt_comm_unique_id and hands the bytes to the other ranks by

@@ -14,7 +14,10 @@ figure is rt_stats.rays / kernel_ms of an awaited frame (RK:114 + RK:153 travers
 "multi1" / "multi4" / "multi8" is rt_trace_rays_multi with k = 1, 4, 8 under the same limits (hit_fraction: hit 0 exists).
 "shade_vs_frame": the 2^20 primary rays of a 1024 x 1024 frame shaded with RT_SHADE_COMPOSE, beside kernel_ms of that frame
 through rt_render -- the same pixels by both routes -- on the reference's scene and on C3's spheres (the query searches the
-spheres by brute force, the frame walks the hierarchy)."""
+spheres by brute force, the frame walks the hierarchy).
+"samples_ref_s2" ... "samples_c3_s4": rt_render_samples (both outputs) of a 1024 x 1024 frame at s = 2 and 4, beside (a) rt_shade_rays
+with RT_SHADE_COMPOSE over the same s*s 2^20 rays resident on the device and (b) kernel_ms of an rt_render frame of
+(1024 s) x (1024 s) -- the same samples by the three routes.  `python tools/query_rate.py samples` runs these alone."""
 import json
 import os
 import sys
@@ -120,8 +123,58 @@ def shade_vs_frame(torch, scene, bounces, mat):
             "shade_ms": round(ms, 4), "shade_rays_per_s": round(rays.shape[0] / ms * 1e3)}
 
 
+def samples_vs_routes(torch, scene, bounces, mat, s):
+    """rt_render_samples of a 1024 x 1024 frame at factor s; rt_shade_rays over its s*s 2^20 sample rays; kernel_ms of the frame of
+    the larger target"""
+    W = H = 1024
+    r = rt.RendererRaytracing(s * W, s * H, scene, maxBounces=bounces).initialize(None, mat)
+    for _ in range(5):
+        r.render()
+    st = r.stats()
+    r.close()
+    r = rt.RendererRaytracing(W, H, scene, maxBounces=bounces).initialize(None, mat)
+    img = torch.empty((H, W, 4), dtype=torch.uint8, device="cuda:0")
+    flt = torch.empty((H, W, 4), dtype=torch.float32, device="cuda:0")
+
+    def timed_ms(run):
+        run()
+        torch.cuda.synchronize()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(REPS):
+            run()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) / REPS
+
+    samples_ms = timed_ms(lambda: r.render_samples(s, out=(img, flt)))
+    rays = ray_tensor(torch, *camera(scene, s * W, s * H, bounces))
+    out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
+    shade_ms = timed_ms(lambda: r.shade_rays(rays, compose=True, out=out))
+    r.close()
+    return {"s": s, "samples": int(rays.shape[0]), "render_samples_ms": round(samples_ms, 4), "shade_rays_ms": round(shade_ms, 4),
+            "frame_kernel_ms": round(st["kernel_ms"], 4), "frame_kernel": st["kernel_id"],
+            "samples_per_s": round(rays.shape[0] / samples_ms * 1e3)}
+
+
+def samples(torch, out):
+    d = np.load(os.path.join(ROOT, "tests", "golden", "ref_scene.npz"))
+    scene = rt.SceneRaytracing.from_packed(d)
+    cfg = rt.BASELINE_CONFIGS["C3"]
+    c3 = rt.synthetic_scene(cfg["spheres"], cfg["seed"])
+    out["build_id"] = rt.abi.load().rt_build_id().decode()
+    for s in (2, 4):
+        out["samples_ref_s%d" % s] = samples_vs_routes(torch, scene, int(d["maxBounces"]), rt.Material.white(), s)
+        out["samples_c3_s%d" % s] = samples_vs_routes(torch, c3, cfg["bounces"], None, s)
+
+
 def main():
     import torch
+    if sys.argv[1:] == ["samples"]:
+        out = {}
+        samples(torch, out)
+        print(json.dumps(out))
+        return
     d = np.load(os.path.join(ROOT, "tests", "golden", "ref_scene.npz"))
     scene = rt.SceneRaytracing.from_packed(d)
     W, H = int(d["W"]), int(d["H"])
@@ -147,6 +200,7 @@ def main():
     r.close()
     out["shade_vs_frame_ref"] = shade_vs_frame(torch, scene, int(d["maxBounces"]), rt.Material.white())
     out["shade_vs_frame_c3"] = shade_vs_frame(torch, c3, cfg["bounces"], None)
+    samples(torch, out)
     print(json.dumps(out))
 
 
