@@ -7,7 +7,7 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-fast-math -Wall -Wn
 SRCS     := $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h)) include/rt355.h
 # identity of the build: profiles (profiles/traffic.json) are evidence for the sources they were taken with
 BUILD_ID := $(shell cat $(SRCS) | sha256sum | cut -c1-16)
-OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o $(CSRC)/rt_query.o $(CSRC)/rt_shade.o $(CSRC)/rt_sample.o
+OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o $(CSRC)/rt_query.o $(CSRC)/rt_shade.o $(CSRC)/rt_sample.o $(CSRC)/rt_gbuffer.o
 
 all: lib oracle node
 
@@ -34,6 +34,10 @@ $(CSRC)/rt_shade.o: $(CSRC)/rt_shade.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_qu
 
 # supersampled frames: rt_shade.o's bounce loops from the camera, resolved on the chip; rt_shade.o's flags exactly
 $(CSRC)/rt_sample.o: $(CSRC)/rt_sample.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
+
+# geometry frames: rt_query.o's walks from the camera, stored as planes; rt_query.o's flags exactly (exactness rests on them)
+$(CSRC)/rt_gbuffer.o: $(CSRC)/rt_gbuffer.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/rt_assemble.o: $(CSRC)/rt_assemble.hip $(CSRC)/rt_types.h include/rt355.h

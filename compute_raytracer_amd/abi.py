@@ -44,6 +44,7 @@ SYMBOLS = [
     "rt_shade_rays", "rt_shade_rays_host",
     "rt_trace_rays_multi", "rt_trace_rays_multi_host",
     "rt_render_samples", "rt_render_samples_host",
+    "rt_render_gbuffer", "rt_render_gbuffer_host",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -82,6 +83,15 @@ class RtShade(ctypes.Structure):
 
 # the same record as a numpy dtype: an (n,) array of it is what rt_shade_rays_host fills
 SHADE_DTYPE = [("r", "<f4"), ("g", "<f4"), ("b", "<f4"), ("dist", "<f4")]
+
+
+class RtGbuffer(ctypes.Structure):
+    """rt_gbuffer (include/rt355.h): the four planes of a geometry frame, any of them NULL but not all; 32 bytes."""
+    _fields_ = [("depth", ctypes.c_void_p), ("normal", ctypes.c_void_p), ("ids", ctypes.c_void_p), ("uv", ctypes.c_void_p)]
+
+
+# the planes of rt_gbuffer in the struct's order: name -> (trailing shape, numpy dtype, alignment of the device form in bytes)
+GBUFFER_PLANES = {"depth": ((), "<f4", 4), "normal": ((4,), "<f4", 16), "ids": ((2,), "<i4", 8), "uv": ((2,), "<f4", 8)}
 
 
 class RtError(RuntimeError):
@@ -194,6 +204,8 @@ def load():
         "rt_trace_rays_multi_host": (ctypes.c_int, [vp, vp, u32, u32, u32, vp]),
         "rt_render_samples": (ctypes.c_int, [vp, u32, vp, sz, vp, sz, vp]),
         "rt_render_samples_host": (ctypes.c_int, [vp, u32, vp, sz, vp, sz]),
+        "rt_render_gbuffer": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(RtGbuffer), sz, vp]),
+        "rt_render_gbuffer_host": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(RtGbuffer), sz]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

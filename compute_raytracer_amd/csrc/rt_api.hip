@@ -1833,6 +1833,98 @@ int rt_render_samples_host(rt_ctx* c, uint32_t ss, uint8_t* rgba8, size_t cap8, 
     return RT_OK;
 }
 
+// ---- geometry frames (rt_gbuffer.hip) ------------------------------------------------------------------------------------------
+
+static_assert(sizeof(rt_gbuffer) == 32, "rt_gbuffer is four pointers");
+
+// The checks of both forms, in the header's order: context, `out`, planes; the state (rt_resize, a scene, rt_write_params); the
+// rectangle; the capacity.  o: the planes as given and the rectangle the call means.
+static int gbuffer_check(const char* who, rt_ctx* c, const uint32_t* rect, const rt_gbuffer* out, size_t cap_pixels, bool device, RtGbufferOut& o) {
+    char msg[200];
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!out) { std::snprintf(msg, sizeof msg, "%s: out is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!out->depth && !out->normal && !out->ids && !out->uv) { std::snprintf(msg, sizeof msg, "%s: all four planes are NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (device && (reinterpret_cast<uintptr_t>(out->depth) % 4u || reinterpret_cast<uintptr_t>(out->normal) % 16u ||
+                   reinterpret_cast<uintptr_t>(out->ids) % 8u || reinterpret_cast<uintptr_t>(out->uv) % 8u)) {
+        std::snprintf(msg, sizeof msg, "%s: depth must be 4-byte, ids and uv 8-byte and normal 16-byte aligned", who);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    if (!c->W || !c->H) { std::snprintf(msg, sizeof msg, "%s: rt_resize has not been called", who); return fail(RT_ERR_STATE, msg); }
+    { int rc = query_scene_written(c, who); if (rc != RT_OK) return rc; }
+    if (!c->have_params) { std::snprintf(msg, sizeof msg, "%s: rt_write_params has not been called", who); return fail(RT_ERR_STATE, msg); }
+    const uint32_t x0 = rect ? rect[0] : 0u, y0 = rect ? rect[1] : 0u, w = rect ? rect[2] : c->W, h = rect ? rect[3] : c->H;
+    if (!w || !h || (uint64_t)x0 + w > c->W || (uint64_t)y0 + h > c->H) {   // full-frame coordinates, whatever the partition
+        std::snprintf(msg, sizeof msg, "%s: the rectangle {%u, %u, %u, %u} is empty or not inside the %u x %u frame", who, x0, y0, w, h, c->W, c->H);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    if (cap_pixels < (size_t)w * h) {
+        std::snprintf(msg, sizeof msg, "%s: a %u x %u rectangle needs room for %zu pixels in every plane", who, w, h, (size_t)w * h);
+        return fail(RT_ERR_CAPACITY, msg);
+    }
+    o.depth = out->depth;
+    o.normal = reinterpret_cast<float4*>(out->normal);
+    o.ids = reinterpret_cast<int2*>(out->ids);
+    o.uv = reinterpret_cast<float2*>(out->uv);
+    o.x0 = x0; o.y0 = y0; o.w = w; o.h = h;
+    o.W = c->W; o.H = c->H;
+    return RT_OK;
+}
+
+// The geometry kernel on `s` behind query_prepare: the camera of the last rt_write_params, by value in the kernel's arguments, and
+// the whole frame's size, whatever the partition -- rt_pick's ray, made in the lane
+static int gbuffer_launch(rt_ctx* c, const RtGbufferOut& o, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+    RtFrameArgs fa;
+    std::memset(&fa, 0, sizeof fa);
+    std::memcpy(fa.p, c->params, sizeof fa.p);
+    fa.W = c->W; fa.H = c->H;
+    if (tri) RT_HIP(rt_launch_gbuffer_triangles(fa, ts, inst, o, s));
+    else RT_HIP(rt_launch_gbuffer_spheres(fa, c->d_records, c->n, o, s));
+    RT_HIP(hipEventRecord(c->ev_query, s));
+    c->query_pending = true;
+    c->query_last = s;
+    return RT_OK;
+}
+
+int rt_render_gbuffer(rt_ctx* c, const uint32_t* rect, const rt_gbuffer* out, size_t cap_pixels, void* hip_stream) {
+    RtGbufferOut o;
+    { int rc = gbuffer_check("rt_render_gbuffer", c, rect, out, cap_pixels, true, o); if (rc != RT_OK) return rc; }
+    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_render_gbuffer", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    return gbuffer_launch(c, o, s, tri, ts, inst);
+}
+
+int rt_render_gbuffer_host(rt_ctx* c, const uint32_t* rect, const rt_gbuffer* out, size_t cap_pixels) {
+    RtGbufferOut o;
+    { int rc = gbuffer_check("rt_render_gbuffer_host", c, rect, out, cap_pixels, false, o); if (rc != RT_OK) return rc; }
+    hipStream_t s;
+    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_render_gbuffer_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    // (one staging buffer of the ray queries, idle between calls, holds the planes asked for one after the other, the widest
+    // first: every plane then starts on a multiple of its own alignment)
+    const size_t px = (size_t)o.w * o.h;
+    const size_t b_normal = out->normal ? px * 16u : 0u, b_ids = out->ids ? px * 8u : 0u, b_uv = out->uv ? px * 8u : 0u, b_depth = out->depth ? px * 4u : 0u;
+    { int rc = grow_staging(c->d_qhits, b_normal + b_ids + b_uv + b_depth); if (rc != RT_OK) return rc; }
+    uint8_t* const base = static_cast<uint8_t*>(c->d_qhits.p);
+    RtGbufferOut d = o;
+    d.normal = out->normal ? reinterpret_cast<float4*>(base) : nullptr;
+    d.ids = out->ids ? reinterpret_cast<int2*>(base + b_normal) : nullptr;
+    d.uv = out->uv ? reinterpret_cast<float2*>(base + b_normal + b_ids) : nullptr;
+    d.depth = out->depth ? reinterpret_cast<float*>(base + b_normal + b_ids + b_uv) : nullptr;
+    { int rc = gbuffer_launch(c, d, s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    if (out->normal) RT_HIP(hipMemcpyAsync(out->normal, d.normal, b_normal, hipMemcpyDeviceToHost, s));
+    if (out->ids) RT_HIP(hipMemcpyAsync(out->ids, d.ids, b_ids, hipMemcpyDeviceToHost, s));
+    if (out->uv) RT_HIP(hipMemcpyAsync(out->uv, d.uv, b_uv, hipMemcpyDeviceToHost, s));
+    if (out->depth) RT_HIP(hipMemcpyAsync(out->depth, d.depth, b_depth, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    return RT_OK;
+}
+
 int rt_device_pixels(rt_ctx* c, void** out_ptr, size_t* out_bytes) {
     if (!c || !out_ptr || !out_bytes) return fail(RT_ERR_INVALID_ARG, "rt_device_pixels: NULL argument");
     if (!c->d_out) return fail(RT_ERR_STATE, "rt_device_pixels: no colour buffer (rt_resize first)");

@@ -87,4 +87,8 @@ struct RtSampleOut {
 };
 hipError_t rt_launch_sample_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtSampleOut& o, hipStream_t s);
 hipError_t rt_launch_sample_spheres(const RtFrameArgs& a, const float* records, uint32_t n_spheres, const RtSampleOut& o, hipStream_t s);
+// Geometry frames (rt_gbuffer.hip; include/rt355.h: rt_render_gbuffer): the nearest hit of the primary ray of every pixel of o's
+// rectangle, as planes.  `a`: the camera words of a.p and a.W = o.W, a.H = o.H (nothing else of it is read).  inst as above.
+hipError_t rt_launch_gbuffer_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtGbufferOut& o, hipStream_t s);
+hipError_t rt_launch_gbuffer_spheres(const RtFrameArgs& a, const float* records, uint32_t n_spheres, const RtGbufferOut& o, hipStream_t s);
 hipError_t rt_launch_pick_rays(const RtFrameArgs& a, const uint32_t* xy, float4* rays, uint32_t n, hipStream_t s);   // xy: [n][2] u32

@@ -83,6 +83,17 @@ struct RtPrepArgs {
     float *geo_w, *lgt_w, *cam_w;
 };
 
+// Geometry frames (rt_gbuffer.hip; include/rt355.h: rt_render_gbuffer): the planes of rt_gbuffer as the kernels store them, each
+// [h][w] of the rectangle {x0, y0, w, h} of the W x H frame and null when not asked for (not all four).
+struct RtGbufferOut {
+    float* depth;              // rt_hit.t
+    float4* normal;            // {rt_hit.normal, 0}
+    int2* ids;                 // {rt_hit.prim, rt_hit.instance}
+    float2* uv;                // {rt_hit.u, rt_hit.v}
+    uint32_t x0, y0, w, h;
+    uint32_t W, H;
+};
+
 struct RtLaunchCfg {
     int mode;      // rt_mode
     int variant;   // kernel variant id; 0 = default

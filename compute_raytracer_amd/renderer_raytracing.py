@@ -408,6 +408,61 @@ class RendererRaytracing:
             cur.wait_stream(run)
         return out
 
+    # ---- geometry frames: depth, normal, ids and uv of what the camera sees, as planes (rt_render_gbuffer / rt_render_gbuffer_host) ----
+    def render_gbuffer(self, rect=None, planes=("depth", "normal", "ids", "uv"), out=None):
+        """pick() over a rectangle of the frame the next render() would show (recalculateScene() first), each field as a dense plane:
+        `depth` (h, w) float32 = t (-1 on a miss), `normal` (h, w, 4) float32 {normal, 0}, `ids` (h, w, 2) int32 {prim, instance}
+        (-1, -1 on a miss), `uv` (h, w, 2) float32.  rect = (x0, y0, w, h) in full-frame pixels, None: the whole frame.  The rays are
+        made on the device and only the planes asked for are stored.
+
+        numpy (out=None): a dict of the arrays named in `planes`, through rt_render_gbuffer_host.  torch: `out` is a dict of
+        contiguous tensors of those shapes and dtypes on this renderer's device, any non-empty subset of the four names (`planes` is
+        then not read) -> `out`, enqueued through rt_render_gbuffer on torch.cuda.current_stream()."""
+        if rect is None:
+            x0, y0, w, h = 0, 0, self.width, self.height
+            c_rect = None
+        else:
+            x0, y0, w, h = (int(v) for v in rect)
+            if min(x0, y0, w, h) < 0 or max(x0, y0, w, h) > 0xFFFFFFFF:
+                raise ValueError("render_gbuffer: rect is (x0, y0, w, h), four unsigned 32-bit numbers")
+            c_rect = (ctypes.c_uint32 * 4)(x0, y0, w, h)
+        if out is not None:
+            return self._render_gbuffer_torch(c_rect, w, h, out)
+        names = [planes] if isinstance(planes, str) else list(planes)
+        if not names or len(set(names)) != len(names) or any(n not in abi.GBUFFER_PLANES for n in names):
+            raise ValueError("render_gbuffer: planes is a non-empty selection of %s" % ", ".join(abi.GBUFFER_PLANES))
+        self.recalculateScene()
+        res = {n: np.zeros((h, w) + abi.GBUFFER_PLANES[n][0], abi.GBUFFER_PLANES[n][1]) for n in names}
+        gb = abi.RtGbuffer(**{n: (a.ctypes.data if a.size else None) for n, a in res.items()})
+        abi.check(self._lib.rt_render_gbuffer_host(self._ctx, c_rect, ctypes.byref(gb), w * h), self._ctx)
+        return res
+
+    def _render_gbuffer_torch(self, c_rect, w, h, out):
+        import torch
+        if not isinstance(out, dict) or not out or any(n not in abi.GBUFFER_PLANES for n in out):
+            raise ValueError("render_gbuffer: out is a dict of tensors named %s" % ", ".join(abi.GBUFFER_PLANES))
+        for n, t in out.items():
+            tail, dtype, _ = abi.GBUFFER_PLANES[n]
+            want = torch.int32 if dtype == "<i4" else torch.float32
+            if type(t).__module__.split(".")[0] != "torch" or t.dtype != want or tuple(t.shape) != (h, w) + tail or not t.is_contiguous():
+                raise ValueError("render_gbuffer: out[%r] must be a contiguous %s tensor of shape %r" % (n, want, (h, w) + tail))
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("render_gbuffer: out must live on cuda:%d, this renderer's device" % self.device)
+        self.recalculateScene()
+        dev = next(iter(out.values())).device
+        cur = torch.cuda.current_stream(dev)
+        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
+        if cur.cuda_stream == 0:
+            if getattr(self, "_query_stream", None) is None:
+                self._query_stream = torch.cuda.Stream(dev)
+            run = self._query_stream
+            run.wait_stream(cur)
+        gb = abi.RtGbuffer(**{n: t.data_ptr() for n, t in out.items()})
+        abi.check(self._lib.rt_render_gbuffer(self._ctx, c_rect, ctypes.byref(gb), w * h, ctypes.c_void_p(run.cuda_stream)), self._ctx)
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
     def pick(self, x, y):
         """What pixel (x, y) of the next frame sees first: its primary ray's nearest hit (full-frame coordinates, scalars or arrays
         that broadcast).  Triangle scenes add `mesh`, the instance's mesh index (-1 on a miss)."""

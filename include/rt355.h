@@ -439,6 +439,44 @@ int rt_shade_rays_host(rt_ctx* ctx, const float* rays, uint32_t n, uint32_t flag
 int rt_render_samples(rt_ctx* ctx, uint32_t s, uint8_t* rgba8, size_t cap8, float* rgbaf, size_t capf, void* hip_stream);   /* device, async */
 int rt_render_samples_host(rt_ctx* ctx, uint32_t s, uint8_t* rgba8, size_t cap8, float* rgbaf, size_t capf);                /* host, sync    */
 
+/* ---- geometry frames: per pixel the depth, normal, ids and barycentrics of what the camera sees ------------------------------- */
+
+typedef struct rt_gbuffer {
+    float*   depth;   /* [h][w]    f32: rt_hit.t of the pixel's primary ray, -1 on a miss       */
+    float*   normal;  /* [h][w][4] f32: rt_hit.normal, word 3 = 0; all 0 on a miss              */
+    int32_t* ids;     /* [h][w][2] i32: {rt_hit.prim, rt_hit.instance}; -1, -1 on a miss        */
+    float*   uv;      /* [h][w][2] f32: {rt_hit.u, rt_hit.v}; 0, 0 for spheres and misses       */
+} rt_gbuffer;         /* any plane may be NULL, not all four */
+
+/* rt_render_gbuffer / rt_render_gbuffer_host: a frame-shaped nearest-hit query that makes its own rays -- rt_pick over a rectangle
+ * of the frame, each field of the hits as a dense plane of its own, and only the planes asked for.  Device form: the planes in device
+ * memory of this context's GPU (depth 4-byte, ids and uv 8-byte, normal 16-byte aligned), enqueued on `hip_stream` (NULL = the
+ * context's stream), returns at once.  Host form: host memory, synchronous, staged through query buffers the context owns, which
+ * grow as needed.
+ *
+ * rect is {x0, y0, w, h} in full-frame pixel coordinates of the last rt_resize, whatever rt_set_partition says (as for rt_pick and
+ * rt_render_samples); NULL is the whole frame.  It is read on the host at the call, in both forms.  The planes are [h][w] of the
+ * rectangle, row 0 at the top; a 1 x 1 rectangle is the device form of rt_pick.  cap_pixels is the number of pixels every non-NULL
+ * plane has room for.
+ *
+ * A pixel.  Pixel (x, y) of the rectangle holds the rt_hit that rt_pick returns for frame pixel (x0 + x, y0 + y), field for field
+ * and bit for bit: the ray of RK:76-86 under the camera of the last rt_write_params, copied at the call, searched as rt_trace_rays
+ * searches (tMin 0.001, the running nearest hit starting at 9999; sphere scenes with the literal loop, every sphere in index order).
+ * No ray and no coordinate is stored anywhere: a lane makes its ray in registers, and a plane that is NULL costs no store.  No sky,
+ * mesh texture, light or maxBounces is read: a missing cube map face is not an error here.
+ *
+ * Contract.  That of rt_trace_rays, word for word: sees every write made before it, per-frame instance writes that no frame has
+ * carried yet included; takes no slot of the event ring, changes no field of rt_stats, has no rt_kernel_id; is unaffected by
+ * rt_select_kernel, rt_set_mode and rt_set_variant; never disturbs frames in flight; queries run in call order, and scene writes
+ * after one wait for it.
+ *
+ * Checks, in this order: a NULL context, a NULL `out`, all four planes NULL, or in the device form a misaligned plane:
+ * RT_ERR_INVALID_ARG.  Then RT_ERR_STATE: no rt_resize, no scene written, or no rt_write_params.  Then a rectangle with w == 0 or
+ * h == 0, or with x0 + w > width or y0 + h > height (the sums taken in 64 bits): RT_ERR_INVALID_ARG.  Then cap_pixels < w * h:
+ * RT_ERR_CAPACITY. */
+int rt_render_gbuffer(rt_ctx* ctx, const uint32_t* rect, const rt_gbuffer* out, size_t cap_pixels, void* hip_stream); /* device, async */
+int rt_render_gbuffer_host(rt_ctx* ctx, const uint32_t* rect, const rt_gbuffer* out, size_t cap_pixels);             /* host, sync   */
+
 /* ---- multi-GPU: render + RCCL gather behind one call (RR:434-470 across a group of GPUs) ------ */
 
 /* One process per GPU.  Rank 0 calls rt_comm_unique_id and hands the bytes to the other ranks by
