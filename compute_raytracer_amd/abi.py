@@ -45,6 +45,7 @@ SYMBOLS = [
     "rt_trace_rays_multi", "rt_trace_rays_multi_host",
     "rt_render_samples", "rt_render_samples_host",
     "rt_render_gbuffer", "rt_render_gbuffer_host",
+    "rt_update_triangles", "rt_refit_blas", "rt_read_nodes", "rt_refit_plan",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -206,6 +207,10 @@ def load():
         "rt_render_samples_host": (ctypes.c_int, [vp, u32, vp, sz, vp, sz]),
         "rt_render_gbuffer": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(RtGbuffer), sz, vp]),
         "rt_render_gbuffer_host": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(RtGbuffer), sz]),
+        "rt_update_triangles": (ctypes.c_int, [vp, u32, u32, fp]),
+        "rt_refit_blas": (ctypes.c_int, [vp, ctypes.POINTER(u32), u32]),
+        "rt_read_nodes": (ctypes.c_int, [vp, u32, u32, fp]),
+        "rt_refit_plan": (ctypes.c_int, [fp, u32, u32, ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32, ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -17,6 +17,8 @@
 #include <vector>
 
 #include "rt_bvh_build.h"
+#include "rt_refit.h"
+#include "rt_refit_plan.h"
 #include "rt_tlas_fit.h"
 
 thread_local std::string g_rt_err;
@@ -273,7 +275,7 @@ int rt_destroy(rt_ctx* c) {
     (void)hipFree(c->d_queue);
     (void)hipFree(c->d_bvh_rec);
     (void)hipFree(c->d_bvh_link);
-    for (rt_ctx::DevBuf* b : {&c->d_tri, &c->d_tri_lookup, &c->d_tex, &c->d_corners, &c->d_flow, &c->d_qrays, &c->d_qhits, &c->d_qxy})
+    for (rt_ctx::DevBuf* b : {&c->d_tri, &c->d_tri_lookup, &c->d_tex, &c->d_corners, &c->d_flow, &c->d_refit_plan, &c->d_qrays, &c->d_qhits, &c->d_qxy})
         (void)hipFree(b->p);
     for (int k = 0; k < kStreams; ++k) { (void)hipFree(c->d_tile_cost[k].p); (void)hipFree(c->d_tile_order[k].p); }
     for (int v = 0; v < kVersions; ++v)
@@ -544,6 +546,13 @@ int rt_write_nodes(rt_ctx* c, size_t byte_offset, const float* data, uint32_t n)
         c->node_count_max = std::max(c->node_count_max, cnt);
     }
     if (n) {                                        // the mirror the relinked copy of the BLAS trees is built from (rt_flow_build.h)
+        // does the write change the STRUCTURE of the trees (a refit plan rests on it, rt_refit_blas)?  The reference's per-frame
+        // rewrite of the top-level nodes usually does not.
+        bool topo = c->h_nodes.size() < end / 4u;
+        for (uint32_t i = 0; i < n && !topo; ++i)
+            topo = std::memcmp(&c->h_nodes[byte_offset / 4u + 8u * (size_t)i + 3u], &data[8u * (size_t)i + 3u], 4) != 0 ||
+                   std::memcmp(&c->h_nodes[byte_offset / 4u + 8u * (size_t)i + 7u], &data[8u * (size_t)i + 7u], 4) != 0;
+        if (topo) ++c->topo_gen;
         if (c->h_nodes.size() < end / 4u) c->h_nodes.resize(end / 4u, 0.0f);
         std::memcpy(reinterpret_cast<char*>(c->h_nodes.data()) + byte_offset, data, bytes);
         if (!c->flow_dirty && end / 32u > c->flow.min_node) c->flow_dirty = true;      // the write reaches nodes the copy was built from
@@ -884,6 +893,7 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
                 if (!stale) all.insert(all.end(), c->flow.roots.begin(), c->flow.roots.end());   // roots already known stay known
                 rt_flow_build(c->h_nodes.data(), n_nodes, all.data(), (uint32_t)all.size(), c->flow);
                 c->flow_dirty = false;
+                ++c->flow_gen;
                 ++c->stats.pair_rebuilds;
                 if (c->flow.ok && c->flow.n_pairs) {
                     int rc = write_buf(c, c->d_flow, 0, c->flow.pairs.data(), (size_t)c->flow.n_pairs * 64u, "flow pairs");
@@ -1400,6 +1410,178 @@ int rt_read_hierarchy(rt_ctx* c, float* rec4, uint32_t* link, uint32_t cap_nodes
     RT_HIP(hipMemcpyAsync(rec4, c->d_bvh_rec, nn * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
     RT_HIP(hipMemcpyAsync(link, c->d_bvh_link, nn * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     RT_HIP(hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
+// ---- deforming meshes: partial triangle writes and the BLAS refit (rt_refit_plan.h, rt_refit.hip) ----------------------------
+
+static_assert(kRefitVersions == (uint32_t)kVersions, "rt_refit.hip stores into every version of the node buffer");
+static_assert((int)kRefitInvalid == (int)RT_ERR_INVALID_ARG && (int)kRefitUnsupported == (int)RT_ERR_UNSUPPORTED, "rt_refit_plan.h returns rt_status codes");
+
+int rt_refit_plan(const float* nodes, uint32_t n_nodes, uint32_t n_tri_lookup, const uint32_t* roots, uint32_t n_roots,
+                  uint32_t* plan, uint32_t cap_nodes, uint32_t* n_plan) {
+    if ((n_nodes && !nodes) || (n_roots && !roots) || !n_plan) return fail(RT_ERR_INVALID_ARG, "rt_refit_plan: NULL argument");
+    *n_plan = 0;
+    std::vector<uint32_t> p;
+    const char* why = "";
+    const int rc = rt_refit_plan_build(nodes, n_nodes, n_tri_lookup, roots, n_roots, p, &why);
+    if (rc != kRefitOk) { char msg[200]; std::snprintf(msg, sizeof msg, "rt_refit_plan: %s", why); return fail(rc, msg); }
+    *n_plan = (uint32_t)(p.size() / 3u);
+    if (p.empty()) return RT_OK;
+    if (cap_nodes < *n_plan || !plan) return fail(RT_ERR_CAPACITY, "rt_refit_plan: need room for n_plan triples");
+    std::memcpy(plan, p.data(), p.size() * sizeof(uint32_t));
+    return RT_OK;
+}
+
+int rt_update_triangles(rt_ctx* c, uint32_t first, uint32_t n, const float* data) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_update_triangles: ctx is NULL");
+    if (c->scene_kind != 1 || !c->d_tri.used) return fail(RT_ERR_STATE, "rt_update_triangles: no triangle scene (rt_write_triangles first)");
+    if ((uint64_t)first + n > c->d_tri.used / 160u) return fail(RT_ERR_INVALID_ARG, "rt_update_triangles: first + n is beyond the triangles written");
+    if (n == 0u) return RT_OK;
+    if (!data) return fail(RT_ERR_INVALID_ARG, "rt_update_triangles: data is NULL");
+    // the corner array follows: rebuilt whole by the next refit, frame or query (ensure_corners) -- one pass over 48 bytes per
+    // lookup slot, cheaper than keeping the inverse of the lookup table to patch single slots
+    c->corners_valid = false;
+    return write_buf(c, c->d_tri, (size_t)first * 160u, data, (size_t)n * 160u, "rt_update_triangles: NULL data");
+}
+
+// the copy of planned node `i` in the pair records (rt_flow_build.h): as the left child of the pair keyed by i, as the right child
+// of the pair keyed by i - 1 -- and of its own pair when i is the last node, where left + 1 clamps
+// (three copies -- the last node of a hand-made buffer as the right child of two pairs -- do not fit the plan's two words: false)
+static bool refit_pair_halves(const RtFlow& f, uint32_t i, uint32_t (&half)[2]) {
+    half[0] = half[1] = 0xFFFFFFFFu;
+    if (f.pair_of[i] != 0xFFFFFFFFu) half[0] = 2u * f.pair_of[i];
+    const bool after = i > 0u && f.pair_of[i - 1u] != 0xFFFFFFFFu, own = i == f.n_nodes - 1u && f.pair_of[i] != 0xFFFFFFFFu;
+    if (after && own) return false;
+    if (after) half[1] = 2u * f.pair_of[i - 1u] + 1u;
+    if (own) half[1] = 2u * f.pair_of[i] + 1u;
+    return true;
+}
+
+int rt_refit_blas(rt_ctx* c, const uint32_t* roots, uint32_t n_roots) {
+    if (!c || (!roots && n_roots)) return fail(RT_ERR_INVALID_ARG, "rt_refit_blas: NULL argument");
+    const uint32_t n_nodes = (uint32_t)(c->nodes_used / 32u), n_slots = (uint32_t)(c->d_tri_lookup.used / 4u);
+    if (c->scene_kind != 1 || !c->d_tri.used || !n_nodes || !n_slots || c->h_nodes.size() / 8u < n_nodes)
+        return fail(RT_ERR_STATE, "rt_refit_blas: no triangle scene (rt_write_triangles, _nodes and _tri_lookup first)");
+    RT_HIP(hipSetDevice(c->device));
+    // ---- which roots ----
+    std::vector<uint32_t> rs;
+    if (roots) {
+        rs.assign(roots, roots + n_roots);
+    } else if (c->inst.blas_on) {                       // every root the current BLAS records name
+        for (size_t i = 0; i + 20u <= c->inst.blas.size(); i += 20u) rs.push_back(rt_flow_u32f(c->inst.blas[i + 16u]));
+    } else if (c->d_blas[0].used) {                     // an instance set written to the device only (more than sixteen)
+        std::vector<float> rec(c->d_blas[0].used / 4u);
+        RT_HIP(hipMemcpy(rec.data(), c->d_blas[0].p, rec.size() * 4u, hipMemcpyDeviceToHost));
+        for (size_t i = 0; i + 20u <= rec.size(); i += 20u) rs.push_back(rt_flow_u32f(rec[i + 16u]));
+    }
+    if (!roots && rs.empty()) return fail(RT_ERR_STATE, "rt_refit_blas: no BLAS records name a root (rt_write_blas first)");
+    std::sort(rs.begin(), rs.end());
+    rs.erase(std::unique(rs.begin(), rs.end()), rs.end());
+    if (rs.empty()) return RT_OK;
+    // ---- the plan: validated on the mirror before anything on the device, in the mirror or in the flags changes ----
+    if (c->refit.topo_gen != c->topo_gen || c->refit.n_tri_lookup != n_slots || c->refit.roots != rs) {
+        std::vector<uint32_t> plan;
+        const char* why = "";
+        const int rc = rt_refit_plan_build(c->h_nodes.data(), n_nodes, n_slots, rs.data(), (uint32_t)rs.size(), plan, &why);
+        if (rc != kRefitOk) { char msg[200]; std::snprintf(msg, sizeof msg, "rt_refit_blas: %s", why); return fail(rc, msg); }
+        c->refit.plan.swap(plan);
+        c->refit.roots = rs;
+        c->refit.topo_gen = c->topo_gen;
+        c->refit.n_tri_lookup = n_slots;
+        c->refit.on_device = false;
+        c->refit.lo = 0xFFFFFFFFu; c->refit.hi = 0u;
+        for (size_t e = 0; e < c->refit.plan.size(); e += 3u) {
+            c->refit.lo = std::min(c->refit.lo, c->refit.plan[e]);
+            c->refit.hi = std::max(c->refit.hi, c->refit.plan[e]);
+        }
+    }
+    const uint32_t n_plan = (uint32_t)(c->refit.plan.size() / 3u);
+    if (n_plan == 0u) return RT_OK;
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    for (int v = 0; v < kVersions; ++v) { int rc = grow_buf(c, c->d_nodes[v], c->nodes_used); if (rc != RT_OK) return rc; }
+    { int rc = ensure_corners(c, c->stream); if (rc != RT_OK) return rc; }
+    if (c->scene_stream && c->scene_stream != c->stream) RT_HIP(hipStreamWaitEvent(c->stream, c->ev_scene, 0));
+    // the pair records hold copies of the boxes: brought up to date by the same kernel while they are current; records that are
+    // stale anyway are rebuilt from the mirror by the frame that needs them
+    bool pairs = !c->flow_dirty && c->flow.ok && c->flow.n_pairs != 0u && c->flow.n_nodes == n_nodes &&
+                 c->d_flow.p && c->d_flow.used >= (size_t)c->flow.n_pairs * 64u;
+    bool pairs_left_behind = false;                     // current records this refit cannot reach: rebuilt by the next frame
+    for (uint32_t e = 0; e < n_plan && pairs; ++e) {
+        uint32_t half[2];
+        if (!refit_pair_halves(c->flow, c->refit.plan[3u * e], half)) { pairs = false; pairs_left_behind = true; }
+    }
+    if (!c->refit.on_device || c->refit.with_pairs != pairs || (pairs && c->refit.flow_gen != c->flow_gen)) {
+        std::vector<uint32_t> dev((size_t)n_plan * kRefitPlanWords);
+        for (uint32_t e = 0; e < n_plan; ++e) {
+            uint32_t* q = &dev[(size_t)e * kRefitPlanWords];
+            q[0] = c->refit.plan[3u * e]; q[1] = c->refit.plan[3u * e + 1u]; q[2] = c->refit.plan[3u * e + 2u];
+            uint32_t half[2] = {0xFFFFFFFFu, 0xFFFFFFFFu};
+            if (pairs) (void)refit_pair_halves(c->flow, q[0], half);
+            q[3] = half[0]; q[4] = half[1];
+        }
+        c->refit.on_device = false;
+        { int rc = grow_buf(c, c->d_refit_plan, dev.size() * 4u); if (rc != RT_OK) return rc; }
+        RT_HIP(hipMemcpyAsync(c->d_refit_plan.p, dev.data(), dev.size() * 4u, hipMemcpyHostToDevice, c->stream));
+        RT_HIP(hipStreamSynchronize(c->stream));        // a pageable source
+        c->refit.on_device = true;
+        c->refit.with_pairs = pairs;
+        c->refit.flow_gen = c->flow_gen;
+    }
+    RtRefitArgs ra;
+    ra.plan = static_cast<const uint32_t*>(c->d_refit_plan.p);
+    ra.n_plan = n_plan;
+    ra.corners = static_cast<const float4*>(c->d_corners.p);
+    ra.n_slots = std::min(n_slots, (uint32_t)(c->d_corners.cap / 48u));
+    ra.n_nodes = n_nodes;
+    for (int v = 0; v < kVersions; ++v) {
+        ra.nodes[v] = static_cast<float*>(c->d_nodes[v].p);
+        ra.n_nodes = std::min(ra.n_nodes, (uint32_t)(c->d_nodes[v].cap / 32u));
+    }
+    ra.pairs = pairs ? static_cast<float*>(c->d_flow.p) : nullptr;
+    ra.n_pairs = pairs ? c->flow.n_pairs : 0u;
+    RT_HIP(rt_launch_refit_nodes(ra, c->stream));
+    RT_HIP(hipEventRecord(c->ev_scene, c->stream));     // frames and queries on other streams wait for it (the scene-update event)
+    c->scene_stream = c->stream;
+    if (pairs_left_behind) c->flow_dirty = true;
+    // ---- the mirror stays what the device holds: the boxes of the planned nodes, read back from version 0 ----
+    const uint32_t lo = c->refit.lo, hi = c->refit.hi;
+    std::vector<float> back((size_t)(hi - lo + 1u) * 8u);
+    RT_HIP(hipMemcpyAsync(back.data(), static_cast<const char*>(c->d_nodes[0].p) + (size_t)lo * 32u, back.size() * 4u, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(hipStreamSynchronize(c->stream));
+    for (uint32_t e = 0; e < n_plan; ++e) {
+        const uint32_t i = c->refit.plan[3u * e];
+        const float* b = &back[(size_t)(i - lo) * 8u];
+        float* m = &c->h_nodes[(size_t)i * 8u];
+        m[0] = b[0]; m[1] = b[1]; m[2] = b[2]; m[4] = b[4]; m[5] = b[5]; m[6] = b[6];
+        // a node inside the head of the buffer also lives in the copy that frames carry (apply_version writes it over the
+        // versions): the same boxes there.  Not a per-frame write: inst.gen stays, the kernel has updated every version.
+        if (i < c->inst.head_nodes && c->inst.head.size() >= (size_t)(i + 1u) * 8u) {
+            float* h = &c->inst.head[(size_t)i * 8u];
+            h[0] = b[0]; h[1] = b[1]; h[2] = b[2]; h[4] = b[4]; h[5] = b[5]; h[6] = b[6];
+        }
+    }
+    return RT_OK;
+}
+
+int rt_read_nodes(rt_ctx* c, uint32_t first_node, uint32_t n, float* dst) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_read_nodes: ctx is NULL");
+    if ((uint64_t)first_node + n > c->nodes_used / 32u) return fail(RT_ERR_INVALID_ARG, "rt_read_nodes: first_node + n is beyond the nodes written");
+    if (n == 0u) return RT_OK;
+    if (!dst) return fail(RT_ERR_INVALID_ARG, "rt_read_nodes: dst is NULL");
+    RT_HIP(hipSetDevice(c->device));
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    // version 0: the one the next frame reads (the event ring is empty).  Per-frame writes of the head of the buffer that no
+    // frame has carried to it yet are laid over the copy, as a frame or a query sees them.
+    { int rc = grow_buf(c, c->d_nodes[0], c->nodes_used); if (rc != RT_OK) return rc; }
+    if (c->scene_stream && c->scene_stream != c->stream) RT_HIP(hipStreamWaitEvent(c->stream, c->ev_scene, 0));
+    RT_HIP(hipMemcpyAsync(dst, static_cast<const char*>(c->d_nodes[0].p) + (size_t)first_node * 32u, (size_t)n * 32u, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(hipStreamSynchronize(c->stream));
+    const uint32_t head = std::min(c->inst.head_nodes, (uint32_t)(c->inst.head.size() / 8u));
+    if (first_node < head) {
+        const uint32_t m = std::min(n, head - first_node);
+        std::memcpy(dst, &c->inst.head[(size_t)first_node * 8u], (size_t)m * 32u);
+    }
     return RT_OK;
 }
 

@@ -137,6 +137,21 @@ struct rt_ctx {
     bool flow_dirty = true;
     uint32_t flow_frames_since = 0, flow_streak = 0, flow_cooldown = 0;   // frames since the last rebuild; consecutive frames that rebuilt; frames left on the node walk
     DevBuf d_flow;                               // the pair records
+    // Deforming meshes (rt_refit_blas; rt_refit_plan.h, rt_refit.hip): the plan of the last refit, kept while nothing it was
+    // made from has changed -- the roots asked for, the tree structure in the mirror, the size of the lookup table -- and its
+    // device copy, which also names the pair records holding a copy of each planned node (valid for one build of the records).
+    uint64_t topo_gen = 1;                       // bumped by every node write that changes a child index, a count or the node count
+    uint64_t flow_gen = 0;                       // bumped by every rebuild of the pair records
+    struct {
+        std::vector<uint32_t> roots, plan;       // sorted unique roots; {node, first_slot, n_slots} per planned node
+        uint64_t topo_gen = 0;                   // 0: no plan
+        uint32_t n_tri_lookup = 0;
+        uint32_t lo = 0, hi = 0;                 // the planned nodes lie in [lo, hi]
+        bool on_device = false;                  // d_refit_plan holds this plan ...
+        bool with_pairs = false;                 // ... with the pair halves of build `flow_gen` of the records (or without any)
+        uint64_t flow_gen = 0;
+    } refit;
+    DevBuf d_refit_plan;
     DevBuf d_tri_dbg;                            // development builds: the triangle kernel's per-workgroup timeline
     // Ray queries (rt_trace_rays_host / rt_pick): their own stream, staging buffers that grow as needed, and the event behind the
     // latest query on any stream -- scene writes wait for it as they wait for the frames in flight (rt_drain)

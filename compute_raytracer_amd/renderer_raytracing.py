@@ -97,6 +97,41 @@ class RendererRaytracing:
         s = np.ascontiguousarray(self.scene.pack_spheres(), dtype=np.float32)    # in place of RR:198-229
         abi.check(L.rt_write_spheres(c, s.ctypes.data_as(fp), s.shape[0]), c)
 
+    # ---- deforming meshes: partial triangle writes and the device refit (rt_update_triangles / rt_refit_blas / rt_read_nodes) ----
+    def update_triangles(self, first, records):
+        """Replaces triangle records [first, first + n) -- (n, 40) float32 in pack_triangles' layout -- on the device and in the
+        scene's packed `triangles` (the scene is uploaded first if it has not been: recalculateScene()).  No node changes: follow
+        it with refit().  Drains the frames in flight."""
+        rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 40)
+        first = int(first)
+        self.recalculateScene()
+        abi.check(self._lib.rt_update_triangles(self._ctx, first, rec.shape[0], rec.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._ctx)
+        tris = np.array(self.scene.static["triangles"], dtype=np.float32)          # a copy: packed arrays may be shared between scenes
+        tris[first:first + rec.shape[0]] = rec
+        self.scene.static["triangles"] = tris
+
+    def refit(self, roots=None):
+        """New boxes for the bottom-level trees under `roots` (node indices: a mesh's root_node; None: every root the instances
+        name), computed on the device from the triangles it holds.  Afterwards the scene's packed `blas_nodes` are the device's
+        bytes, so scene.to_packed() describes exactly what frames and queries read.  The top-level tree is built from the meshes'
+        placeholder boxes (scene-raytracing.ts) and does not change.  Drains the frames in flight."""
+        self.recalculateScene()
+        if roots is None:
+            abi.check(self._lib.rt_refit_blas(self._ctx, None, 0), self._ctx)
+        else:
+            r = np.ascontiguousarray(np.asarray(roots, dtype=np.int64).reshape(-1).astype(np.uint32))
+            abi.check(self._lib.rt_refit_blas(self._ctx, r.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), r.shape[0]), self._ctx)
+        self.scene.static["blas_nodes"] = self.read_nodes(self.scene.tlasNodesMax, self.scene.blasNodesUsed)
+
+    def read_nodes(self, first=0, n=None):
+        """(n, 8) float32: nodes [first, first + n) of the node buffer as the next frame would read them (n None: up to the end of
+        the scene's buffer).  A diagnostic: it waits for the frames in flight."""
+        first = int(first)
+        n = self.scene.node_buffer_length() - first if n is None else int(n)
+        out = np.zeros((max(n, 0), 8), dtype=np.float32)
+        abi.check(self._lib.rt_read_nodes(self._ctx, first, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._ctx)
+        return out
+
     # ---- RR:434-470 -----------------------------------------------------------------------
     def render(self):
         import time

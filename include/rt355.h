@@ -579,6 +579,46 @@ int rt_order_tiles(rt_ctx* ctx, const uint32_t* cost, uint32_t n, uint32_t wave_
  * RT_ERR_CAPACITY when cap_nodes < n_nodes + 1 (*n_nodes is set either way). */
 int rt_read_hierarchy(rt_ctx* ctx, float* rec4, uint32_t* link, uint32_t cap_nodes, uint32_t* n_nodes);
 
+/* ---- deforming meshes: partial triangle writes and a refit of the bottom-level trees on the device ------------------------------ */
+
+/* rt_update_triangles: queue.writeBuffer(triangleBuffer, first * 160, data) -- replaces records [first, first + n) of the triangle
+ * buffer, in the layout of rt_write_triangles, from host memory.  A scene-setup call: it waits for the frames in flight, and frames
+ * and queries after it see the new records (the library's corner array follows by itself).  On its own it changes no node: it is
+ * exactly a partial rt_write_triangles.  first + n (taken in 64 bits) beyond the triangles written: RT_ERR_INVALID_ARG, nothing
+ * changes; n == 0: RT_OK.
+ *
+ * rt_refit_blas: new boxes for every node of the bottom-level trees under `roots` -- node indices, the rootNodeIndex values of the
+ * BLAS records as u32(f32) reads them; duplicates are refitted once; roots == NULL with n_roots == 0: every root the current BLAS
+ * records name.  The box of a node is, per axis, fminf / fmaxf over the three float32 corners of every triangle in the leaves
+ * below it, starting from (float)1e30 and (float)-1e30 (a NaN corner is skipped): exact, so a tree whose vertices did not move
+ * comes back bit for bit as the project's builders made it.  Words 3 and 7 of a node are never written, and no node outside the
+ * named trees is: the top-level nodes stay the host's (it reads the new root boxes through rt_read_nodes if it wants them).
+ * The trees are walked on the host first, on the library's mirror of the node buffer, nothing clamped: a reached node index at
+ * or beyond the node count, a leaf run beyond the lookup table, or a node reached twice over all the roots (sharing, a cycle):
+ * RT_ERR_INVALID_ARG; a node whose leaves do not form one contiguous run of lookup slots (no builder makes one):
+ * RT_ERR_UNSUPPORTED; either way nothing on the device or in the context has changed.  The walk is kept while the structure of
+ * the trees, the lookup table's size and the roots stay the same.  The boxes are computed on the device (rt_refit.hip) and
+ * stored into every copy a kernel reads: all versions of the node buffer and the library's relinked pair records -- a refit
+ * does not make the next frame rebuild those (rt_stats.pair_rebuilds).  Synchronous, and a scene-setup call: waits for the
+ * frames in flight.
+ *
+ * Both: RT_ERR_STATE without a triangle scene; a NULL context (or NULL data / roots with a non-zero count): RT_ERR_INVALID_ARG. */
+int rt_update_triangles(rt_ctx* ctx, uint32_t first, uint32_t n, const float* data);      /* host memory */
+int rt_refit_blas(rt_ctx* ctx, const uint32_t* roots, uint32_t n_roots);
+
+/* Diagnostic: copies `n` nodes (8 f32 each) starting at node `first_node` from the device to `dst` -- the version of the node
+ * buffer the next frame would read, with per-frame writes of its head applied, as a frame or a query sees them.  Waits for the
+ * frames in flight.  first_node + n beyond the nodes written: RT_ERR_INVALID_ARG. */
+int rt_read_nodes(rt_ctx* ctx, uint32_t first_node, uint32_t n, float* dst);
+
+/* Runs the HOST side of rt_refit_blas on its own (no device, no context): the validation above and its result, one triple
+ * {node, first_slot, n_slots} per reached node (roots ascending, each tree depth-first, the left child first): the node's box is
+ * the min / max over lookup slots [first_slot, first_slot + n_slots).  `nodes` as rt_write_nodes receives them, n_tri_lookup
+ * the length of the triangle lookup table.  Returns rt_refit_blas' status codes; RT_ERR_CAPACITY when cap_nodes < *n_plan
+ * (*n_plan is set either way; 0 on the other failures). */
+int rt_refit_plan(const float* nodes, uint32_t n_nodes, uint32_t n_tri_lookup, const uint32_t* roots, uint32_t n_roots,
+                  uint32_t* plan, uint32_t cap_nodes, uint32_t* n_plan);
+
 /* Which filter forms a frame of this scene may use (no device needed): *filter_ok = 0 when
  * max(|center| + |radius| over the spheres, |cameraPos|, |lightPosition|) is NaN, infinite or
  * >= 2^20 -- fast mode then renders the frame with the literal kernel --, *signed_filter = 1 when
