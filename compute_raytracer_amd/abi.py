@@ -46,6 +46,7 @@ SYMBOLS = [
     "rt_render_samples", "rt_render_samples_host",
     "rt_render_gbuffer", "rt_render_gbuffer_host",
     "rt_update_triangles", "rt_refit_blas", "rt_read_nodes", "rt_refit_plan",
+    "rt_build_blas", "rt_read_tri_lookup", "rt_build_blas_host",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -93,6 +94,15 @@ class RtGbuffer(ctypes.Structure):
 
 # the planes of rt_gbuffer in the struct's order: name -> (trailing shape, numpy dtype, alignment of the device form in bytes)
 GBUFFER_PLANES = {"depth": ((), "<f4", 4), "normal": ((4,), "<f4", 16), "ids": ((2,), "<i4", 8), "uv": ((2,), "<f4", 8)}
+
+
+class RtBlasRange(ctypes.Structure):
+    """rt_blas_range (include/rt355.h): the nodes and lookup slots one tree of rt_build_blas may use, 16 bytes."""
+    _fields_ = [("root_node", ctypes.c_uint32), ("node_cap", ctypes.c_uint32), ("first_slot", ctypes.c_uint32), ("n_slots", ctypes.c_uint32)]
+
+
+# the same record as a numpy dtype: an (n,) array of it is what rt_build_blas takes
+BLAS_RANGE_DTYPE = [("root_node", "<u4"), ("node_cap", "<u4"), ("first_slot", "<u4"), ("n_slots", "<u4")]
 
 
 class RtError(RuntimeError):
@@ -211,6 +221,9 @@ def load():
         "rt_refit_blas": (ctypes.c_int, [vp, ctypes.POINTER(u32), u32]),
         "rt_read_nodes": (ctypes.c_int, [vp, u32, u32, fp]),
         "rt_refit_plan": (ctypes.c_int, [fp, u32, u32, ctypes.POINTER(u32), u32, ctypes.POINTER(u32), u32, ctypes.POINTER(u32)]),
+        "rt_build_blas": (ctypes.c_int, [vp, ctypes.POINTER(RtBlasRange), u32, ctypes.POINTER(u32)]),
+        "rt_read_tri_lookup": (ctypes.c_int, [vp, u32, u32, fp]),
+        "rt_build_blas_host": (ctypes.c_int, [fp, u32, fp, u32, fp, u32, ctypes.POINTER(RtBlasRange), u32, ctypes.POINTER(u32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -19,6 +19,7 @@
 #include "rt_bvh_build.h"
 #include "rt_refit.h"
 #include "rt_refit_plan.h"
+#include "rt_build.h"
 #include "rt_tlas_fit.h"
 
 thread_local std::string g_rt_err;
@@ -275,7 +276,7 @@ int rt_destroy(rt_ctx* c) {
     (void)hipFree(c->d_queue);
     (void)hipFree(c->d_bvh_rec);
     (void)hipFree(c->d_bvh_link);
-    for (rt_ctx::DevBuf* b : {&c->d_tri, &c->d_tri_lookup, &c->d_tex, &c->d_corners, &c->d_flow, &c->d_refit_plan, &c->d_qrays, &c->d_qhits, &c->d_qxy})
+    for (rt_ctx::DevBuf* b : {&c->d_tri, &c->d_tri_lookup, &c->d_tex, &c->d_corners, &c->d_flow, &c->d_refit_plan, &c->d_build, &c->d_qrays, &c->d_qhits, &c->d_qxy})
         (void)hipFree(b->p);
     for (int k = 0; k < kStreams; ++k) { (void)hipFree(c->d_tile_cost[k].p); (void)hipFree(c->d_tile_order[k].p); }
     for (int v = 0; v < kVersions; ++v)
@@ -1582,6 +1583,136 @@ int rt_read_nodes(rt_ctx* c, uint32_t first_node, uint32_t n, float* dst) {
         const uint32_t m = std::min(n, head - first_node);
         std::memcpy(dst, &c->inst.head[(size_t)first_node * 8u], (size_t)m * 32u);
     }
+    return RT_OK;
+}
+
+// ---- device BLAS builds (rt_blas_build.h: the arithmetic and the host model; rt_build.hip: the kernels) -------------------------
+
+static_assert(kBuildVersions == (uint32_t)kVersions, "rt_build.hip stores into every version of the node buffer");
+
+int rt_build_blas_host(const float* triangles, uint32_t n_triangles, float* tri_lookup, uint32_t n_tri_lookup, float* nodes,
+                       uint32_t n_nodes, const rt_blas_range* ranges, uint32_t n, uint32_t* used) {
+    const char* why = "";
+    const int rc = rt_bb_build_host(triangles, n_triangles, tri_lookup, n_tri_lookup, nodes, n_nodes, ranges, n, used, &why);
+    if (rc != RT_OK) { char msg[200]; std::snprintf(msg, sizeof msg, "rt_build_blas_host: %s", why); return fail(rc, msg); }
+    return RT_OK;
+}
+
+int rt_build_blas(rt_ctx* c, const rt_blas_range* ranges, uint32_t n, uint32_t* used) {
+    if (!c || (!ranges && n)) return fail(RT_ERR_INVALID_ARG, "rt_build_blas: NULL argument");
+    const uint32_t n_nodes = (uint32_t)(c->nodes_used / 32u), n_slots = (uint32_t)(c->d_tri_lookup.used / 4u);
+    const uint32_t n_tri = (uint32_t)(c->d_tri.used / 160u);
+    if (c->scene_kind != 1 || !n_tri || !n_nodes || !n_slots || c->h_nodes.size() / 8u < n_nodes)
+        return fail(RT_ERR_STATE, "rt_build_blas: no triangle scene (rt_write_triangles, _nodes and _tri_lookup first)");
+    if (n == 0u) return RT_OK;
+    if (const char* bad = rt_bb_check_ranges(ranges, n, n_nodes, n_slots)) {
+        char msg[200]; std::snprintf(msg, sizeof msg, "rt_build_blas: %s", bad); return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    RT_HIP(hipSetDevice(c->device));
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    for (int v = 0; v < kVersions; ++v) { int rc = grow_buf(c, c->d_nodes[v], c->nodes_used); if (rc != RT_OK) return rc; }
+    if (c->scene_stream && c->scene_stream != c->stream) RT_HIP(hipStreamWaitEvent(c->stream, c->ev_scene, 0));
+    // ---- scratch: 2 n_slots - 1 build nodes per range always suffice (a split leaves both sides non-empty) ----
+    uint64_t cap64 = 0;
+    for (uint32_t i = 0; i < n; ++i) cap64 += 2u * (uint64_t)ranges[i].n_slots - 1u;
+    if (cap64 > 0x7FFFFFFFu) return fail(RT_ERR_CAPACITY, "rt_build_blas: too many lookup slots for one call");
+    const uint32_t node_cap = (uint32_t)cap64;
+    size_t at = 0;
+    auto carve = [&](size_t bytes) { const size_t o = at; at += (bytes + 15u) & ~(size_t)15u; return o; };
+    const size_t o_ranges = carve((size_t)n * sizeof(rt_blas_range)), o_prim = carve((size_t)n_slots * sizeof(RtBbPrim));
+    const size_t o_ord0 = carve((size_t)n_slots * 4u), o_ord1 = carve((size_t)n_slots * 4u), o_final = carve((size_t)n_slots * 4u);
+    const size_t o_node = carve((size_t)node_cap * sizeof(RtBuildNode)), o_dec = carve((size_t)node_cap * sizeof(RtBuildDec));
+    const size_t o_sub = carve((size_t)node_cap * 4u), o_rank = carve((size_t)node_cap * 4u), o_index = carve((size_t)node_cap * 4u);
+    const size_t o_root = carve((size_t)node_cap * 4u), o_next = carve(4u);
+    { int rc = grow_buf(c, c->d_build, at); if (rc != RT_OK) return rc; }
+    char* base = static_cast<char*>(c->d_build.p);
+    RtBuildArgs ba;
+    ba.tri = static_cast<const float*>(c->d_tri.p); ba.n_tri = n_tri;
+    ba.lookup = static_cast<float*>(c->d_tri_lookup.p); ba.n_slots = std::min(n_slots, (uint32_t)(c->d_tri_lookup.cap / 4u));
+    ba.n_nodes = n_nodes;
+    for (int v = 0; v < kVersions; ++v) {
+        ba.nodes[v] = static_cast<float*>(c->d_nodes[v].p);
+        ba.n_nodes = std::min(ba.n_nodes, (uint32_t)(c->d_nodes[v].cap / 32u));
+    }
+    ba.ranges = reinterpret_cast<const rt_blas_range*>(base + o_ranges); ba.n_ranges = n;
+    ba.prim = reinterpret_cast<RtBbPrim*>(base + o_prim);
+    ba.order[0] = reinterpret_cast<uint32_t*>(base + o_ord0); ba.order[1] = reinterpret_cast<uint32_t*>(base + o_ord1);
+    ba.final_order = reinterpret_cast<uint32_t*>(base + o_final);
+    ba.node = reinterpret_cast<RtBuildNode*>(base + o_node); ba.dec = reinterpret_cast<RtBuildDec*>(base + o_dec);
+    ba.sub = reinterpret_cast<uint32_t*>(base + o_sub); ba.rank = reinterpret_cast<uint32_t*>(base + o_rank);
+    ba.index = reinterpret_cast<uint32_t*>(base + o_index); ba.root = reinterpret_cast<uint32_t*>(base + o_root);
+    ba.node_cap = node_cap;
+    ba.next_count = reinterpret_cast<uint32_t*>(base + o_next);
+    hipStream_t s = c->stream;
+    RT_HIP(hipMemcpyAsync(base + o_ranges, ranges, (size_t)n * sizeof(rt_blas_range), hipMemcpyHostToDevice, s));
+    RT_HIP(hipStreamSynchronize(s));                    // a pageable source
+    // ---- the levels: the host learns one word per level, the next level's node count ----
+    RT_HIP(rt_launch_build_prep(ba, ranges, s));
+    std::vector<uint32_t> off(1, 0u), cnt(1, n);
+    while (cnt.back() != 0u) {
+        const uint32_t level = (uint32_t)cnt.size() - 1u;
+        RT_HIP(rt_launch_build_level(ba, level, off[level], cnt[level], s));
+        uint32_t next = 0u;
+        RT_HIP(hipMemcpyAsync(&next, ba.next_count, 4u, hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));
+        const uint32_t o = off[level] + cnt[level];
+        if (next > node_cap - o) return fail(RT_ERR_HIP, "rt_build_blas: a level beyond the build's node capacity (corrupt scratch state)");
+        off.push_back(o);
+        cnt.push_back(next);
+    }
+    const uint32_t levels = (uint32_t)cnt.size() - 1u;  // the last entry is the empty level
+    for (uint32_t l = levels; l-- > 0u;) RT_HIP(rt_launch_build_count_up(ba, off[l], cnt[l], s));
+    // ---- sizing before committing: nothing of the scene has been written so far ----
+    std::vector<uint32_t> sub(n);
+    RT_HIP(hipMemcpyAsync(sub.data(), ba.sub, (size_t)n * 4u, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    bool fits = true;
+    uint32_t worst = 0u;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t u = 1u + 2u * sub[i];
+        if (used) used[i] = u;
+        if (u > ranges[i].node_cap) { if (fits) worst = i; fits = false; }
+    }
+    if (!fits) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "rt_build_blas: the tree of range %u needs %u nodes, its node_cap is %u", worst, 1u + 2u * sub[worst], ranges[worst].node_cap);
+        return fail(RT_ERR_CAPACITY, msg);
+    }
+    for (uint32_t l = 0; l < levels; ++l) RT_HIP(rt_launch_build_rank_down(ba, off[l], cnt[l], s));
+    for (uint32_t l = 0; l < levels; ++l) RT_HIP(rt_launch_build_emit_nodes(ba, off[l], cnt[l], s));
+    RT_HIP(rt_launch_build_emit_lookup(ba, ranges, s));
+    RT_HIP(hipEventRecord(c->ev_scene, s));             // frames and queries on other streams wait for it (the scene-update event)
+    c->scene_stream = s;
+    // ---- the mirror follows: whole records, read back from version 0 ----
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t u = 1u + 2u * sub[i];
+        RT_HIP(hipMemcpyAsync(&c->h_nodes[(size_t)ranges[i].root_node * 8u], static_cast<const char*>(c->d_nodes[0].p) + (size_t)ranges[i].root_node * 32u,
+                              (size_t)u * 32u, hipMemcpyDeviceToHost, s));
+    }
+    RT_HIP(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t r0 = ranges[i].root_node, u = 1u + 2u * sub[i];
+        for (uint32_t k = r0; k < r0 + u; ++k) c->node_count_max = std::max(c->node_count_max, rt_flow_u32f(c->h_nodes[(size_t)k * 8u + 7u]));
+        // nodes inside the head of the buffer also live in the copy that frames carry (apply_version writes it over the versions)
+        const uint32_t head = std::min(c->inst.head_nodes, (uint32_t)(c->inst.head.size() / 8u));
+        if (r0 < head) std::memcpy(&c->inst.head[(size_t)r0 * 8u], &c->h_nodes[(size_t)r0 * 8u], (size_t)std::min(u, head - r0) * 32u);
+    }
+    ++c->topo_gen;                                      // a refit plan rests on the structure
+    c->flow_dirty = true;                               // a node write reached the trees: the next frame rebuilds the pair records
+    c->corners_valid = false;                           // the lookup table moved
+    return RT_OK;
+}
+
+int rt_read_tri_lookup(rt_ctx* c, uint32_t first_slot, uint32_t n, float* dst) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_read_tri_lookup: ctx is NULL");
+    if ((uint64_t)first_slot + n > c->d_tri_lookup.used / 4u) return fail(RT_ERR_INVALID_ARG, "rt_read_tri_lookup: first_slot + n is beyond the slots written");
+    if (n == 0u) return RT_OK;
+    if (!dst) return fail(RT_ERR_INVALID_ARG, "rt_read_tri_lookup: dst is NULL");
+    RT_HIP(hipSetDevice(c->device));
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    if (c->scene_stream && c->scene_stream != c->stream) RT_HIP(hipStreamWaitEvent(c->stream, c->ev_scene, 0));
+    RT_HIP(hipMemcpyAsync(dst, static_cast<const char*>(c->d_tri_lookup.p) + (size_t)first_slot * 4u, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(hipStreamSynchronize(c->stream));
     return RT_OK;
 }
 

@@ -152,6 +152,7 @@ struct rt_ctx {
         uint64_t flow_gen = 0;
     } refit;
     DevBuf d_refit_plan;
+    DevBuf d_build;                              // scratch of rt_build_blas (rt_build.h: RtBuildArgs), kept between calls
     DevBuf d_tri_dbg;                            // development builds: the triangle kernel's per-workgroup timeline
     // Ray queries (rt_trace_rays_host / rt_pick): their own stream, staging buffers that grow as needed, and the event behind the
     // latest query on any stream -- scene writes wait for it as they wait for the frames in flight (rt_drain)

@@ -132,6 +132,43 @@ class RendererRaytracing:
         abi.check(self._lib.rt_read_nodes(self._ctx, first, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._ctx)
         return out
 
+    # ---- device BLAS builds (rt_build_blas / rt_read_tri_lookup) ----
+    def rebuild(self, meshes=None):
+        """The bottom-level trees of `meshes` (indices into scene.meshes; None: all of them) built anew on the device from the
+        triangles it holds: the host builder's SAH tree of the mesh as it is now, where refit() only moves the boxes of the tree
+        it was given.  Each tree may use the nodes from its mesh's root up to the next mesh's root (the end of the buffer for the
+        last one): a tree that needs more raises RtError(RT_ERR_CAPACITY) with the counts, and nothing has changed -- lay such a
+        scene out with createTriangleScene(..., node_capacity="full").  Afterwards the scene's packed `blas_nodes` and
+        `tri_lookup` are the device's bytes.  Returns the node count of each tree built.  Drains the frames in flight."""
+        self.recalculateScene()
+        sc = self.scene
+        which = list(range(len(sc.meshes))) if meshes is None else [int(m) for m in meshes]
+        roots = sorted(m.root_node for m in sc.meshes) + [sc.node_buffer_length()]
+        ranges = np.zeros(len(which), dtype=abi.BLAS_RANGE_DTYPE)
+        for k, m in enumerate(which):
+            mesh = sc.meshes[m]
+            nxt = min(r for r in roots if r > mesh.root_node)
+            ranges[k] = (mesh.root_node, nxt - mesh.root_node, mesh.lookup_offset, mesh.soup.count)
+        used = np.zeros(max(len(which), 1), dtype=np.uint32)
+        rc = self._lib.rt_build_blas(self._ctx, ranges.ctypes.data_as(ctypes.POINTER(abi.RtBlasRange)), len(which),
+                                     used.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+        if rc == abi.RT_ERR_CAPACITY:
+            short = ["mesh %d needs %d nodes, has %d" % (m, u, r["node_cap"]) for m, u, r in zip(which, used, ranges) if u > r["node_cap"]]
+            raise abi.RtError(rc, "rebuild: " + "; ".join(short) + ' (createTriangleScene(..., node_capacity="full") reserves 2 T - 1 per mesh)')
+        abi.check(rc, self._ctx)
+        sc.static["blas_nodes"] = self.read_nodes(sc.tlasNodesMax, sc.blasNodesUsed)
+        sc.static["tri_lookup"] = self.read_tri_lookup()
+        return [int(u) for u in used[:len(which)]]
+
+    def read_tri_lookup(self, first=0, n=None):
+        """(n,) float32: slots [first, first + n) of the triangle lookup table on the device (n None: up to the end of the scene's
+        table).  A diagnostic: it waits for the frames in flight."""
+        first = int(first)
+        n = self.scene.triangleCount - first if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=np.float32)
+        abi.check(self._lib.rt_read_tri_lookup(self._ctx, first, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._ctx)
+        return out
+
     # ---- RR:434-470 -----------------------------------------------------------------------
     def render(self):
         import time

@@ -130,8 +130,12 @@ class SceneRaytracing:
             self.buildTopLevel()
 
     # ---- the reference's live scene type: meshes + instances + two-level tree (SR:47-272) --------
-    def createTriangleScene(self, meshes, instances):
-        """meshes: TriMesh list; instances: Instances (or the records Instances.from_records takes)."""
+    def createTriangleScene(self, meshes, instances, node_capacity="tight"):
+        """meshes: TriMesh list; instances: Instances (or the records Instances.from_records takes).  node_capacity: "tight" packs
+        the meshes' trees back to back, as the reference does; "full" reserves 2 T - 1 nodes per mesh of T triangles -- what any
+        tree of it can need, so that RendererRaytracing.rebuild() always fits -- and leaves zero records in the gaps."""
+        if node_capacity not in ("tight", "full"):
+            raise ValueError('node_capacity is "tight" or "full"')
         from .instances import Instances
         if self.camera is None:
             self.createScene([])
@@ -146,12 +150,15 @@ class SceneRaytracing:
         nodes = 0
         for mesh in self.meshes:                               # SR:116-120
             mesh.root_node = self.tlasNodesMax + nodes
-            nodes += mesh.tree.used
+            nodes += mesh.tree.used if node_capacity == "tight" else max(mesh.tree.used, 2 * mesh.soup.count - 1)
         self.blasNodesUsed = nodes
         z40, z8 = np.zeros((0, 40), np.float32), np.zeros((0, 8), np.float32)
+        ends = [m.root_node for m in self.meshes[1:]] + [self.tlasNodesMax + nodes]
         self.static = dict(
             triangles=np.concatenate([m.soup.pack() for m in self.meshes] + [z40]),                       # RR:198-209
-            blas_nodes=np.concatenate([m.tree.nodes(m.root_node, m.lookup_offset) for m in self.meshes] + [z8]),   # RR:212-223, SR:256-272
+            blas_nodes=np.concatenate([np.concatenate([m.tree.nodes(m.root_node, m.lookup_offset),
+                                                       np.zeros((end - m.root_node - m.tree.used, 8), np.float32)])
+                                       for m, end in zip(self.meshes, ends)] + [z8]),                     # RR:212-223, SR:256-272
             tri_lookup=np.concatenate([(m.tree.order + m.lookup_offset).astype(np.float64) for m in self.meshes]
                                       + [np.zeros(0)]).astype(np.float32))                                # RR:225-229, SR:82-93
         self.buildTopLevel()

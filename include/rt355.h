@@ -619,6 +619,42 @@ int rt_read_nodes(rt_ctx* ctx, uint32_t first_node, uint32_t n, float* dst);
 int rt_refit_plan(const float* nodes, uint32_t n_nodes, uint32_t n_tri_lookup, const uint32_t* roots, uint32_t n_roots,
                   uint32_t* plan, uint32_t cap_nodes, uint32_t* n_plan);
 
+/* ---- device BLAS builds: the builder's SAH tree of a mesh, made on the device ------------------------------------------------------ */
+
+typedef struct rt_blas_range {
+    uint32_t root_node;   /* node index of the tree's root (a BLAS record's rootNodeIndex)                */
+    uint32_t node_cap;    /* nodes [root_node, root_node + node_cap) are this tree's to use               */
+    uint32_t first_slot;  /* the tree's triangles: u32(triangleLookup[first_slot .. first_slot+n_slots)) */
+    uint32_t n_slots;
+} rt_blas_range;
+
+/* rt_build_blas: for each range, the tree the project's host builder (the reference's bvh.ts: SAH over nine planes per axis at
+ * tenths of the node's extent) makes of the triangles the range's lookup slots name, from the float32 corners the device holds
+ * (indices clamped to the triangles written).  The root goes to root_node, child pairs are numbered depth-first, the left subtree
+ * first, from root_node + 1; word 3 is the child index or a leaf's first slot, word 7 the count; boxes are the exact float32
+ * min / max.  The range's lookup slots are permuted so that every leaf owns a contiguous run; inside a leaf the slots keep the
+ * relative order they had before the call, so a second build of unchanged triangles changes no byte.  used[i] (when not NULL) is
+ * the tree's node count; nodes [root_node + used, root_node + node_cap) are not touched.  2 * n_slots - 1 nodes always suffice.
+ * Checks, in this order: a NULL context, or NULL ranges with n != 0: RT_ERR_INVALID_ARG; no triangle scene (triangles, nodes and
+ * lookup written): RT_ERR_STATE; n == 0: RT_OK; a range with n_slots == 0 or node_cap == 0, beyond the nodes or slots written
+ * (sums in 64 bits), covering node 0, or overlapping another in nodes or in slots: RT_ERR_INVALID_ARG, nothing changed; a tree
+ * that needs more than node_cap nodes: RT_ERR_CAPACITY -- used[] is set for every range, and nothing of the scene has changed.
+ * Non-finite corners: the call ends, is memory-safe and leaves every slot in exactly one leaf of a well-formed tree; no shape is
+ * promised.  Synchronous, and a scene-setup call: waits for the frames in flight.  Afterwards every version of the node buffer,
+ * the library's mirror and the head copy that frames carry hold the new records, the relinked pair records are stale -- the next
+ * frame rebuilds them (rt_stats.pair_rebuilds) --, and the corner array and any refit plan are remade when next needed. */
+int rt_build_blas(rt_ctx* ctx, const rt_blas_range* ranges, uint32_t n, uint32_t* used /* [n], may be NULL */);
+
+/* Diagnostic: rt_read_nodes for the triangle lookup table -- `n` words starting at slot `first_slot`.  Waits for the frames in
+ * flight.  first_slot + n beyond the slots written: RT_ERR_INVALID_ARG. */
+int rt_read_tri_lookup(rt_ctx* ctx, uint32_t first_slot, uint32_t n, float* dst);
+
+/* Runs rt_build_blas' algorithm on caller arrays in place, serially, with no device and no context: the same inline arithmetic
+ * as the kernels (csrc/rt_blas_build.h), the same checks and results.  triangles: 40 floats each; nodes: 8 floats each.
+ * RT_ERR_STATE when an array is NULL or empty. */
+int rt_build_blas_host(const float* triangles, uint32_t n_triangles, float* tri_lookup, uint32_t n_tri_lookup,
+                       float* nodes, uint32_t n_nodes, const rt_blas_range* ranges, uint32_t n, uint32_t* used);
+
 /* Which filter forms a frame of this scene may use (no device needed): *filter_ok = 0 when
  * max(|center| + |radius| over the spheres, |cameraPos|, |lightPosition|) is NaN, infinite or
  * >= 2^20 -- fast mode then renders the frame with the literal kernel --, *signed_filter = 1 when
