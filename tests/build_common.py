@@ -97,11 +97,59 @@ def helper_mesh_records():
     return [m.soup.pack() for m in scene.meshes]
 
 
+def skew_records(n=48, seed=7):
+    """n small triangles whose centroids fall geometrically along x (x_k = 10^(-k/2), extents of about 1 % of x_k): every split
+    peels the farthest few off, so build_tree makes a long chain of levels two or four nodes wide"""
+    rng = np.random.default_rng(seed)
+    x = 10.0 ** (-np.arange(n) / 2.0)
+    centre = np.stack([x, np.zeros(n), np.zeros(n)], axis=1)[:, None, :]
+    return records_of((centre + 0.01 * x[:, None, None] * rng.uniform(-1.0, 1.0, (n, 3, 3))).astype(F))
+
+
+# runs of exactly a wave (64), two (128), the longest short run (256: kBuildShort), two whole chunks of the block partition (512)
+# and one past them
 MESHES = {"T1": lambda: random_records(1, 101), "T2": lambda: random_records(2, 102), "T3": lambda: random_records(3, 103),
-          "T65": lambda: random_records(65, 165), "T257": lambda: random_records(257, 357), "T1000": lambda: random_records(1000, 1100),
-          "grid": grid_records, "duplicates": duplicate_records,
+          "T64": lambda: random_records(64, 164), "T65": lambda: random_records(65, 165), "T128": lambda: random_records(128, 228),
+          "T256": lambda: random_records(256, 356), "T257": lambda: random_records(257, 357), "T512": lambda: random_records(512, 612),
+          "T513": lambda: random_records(513, 613), "T1000": lambda: random_records(1000, 1100),
+          "grid": grid_records, "duplicates": duplicate_records, "skew": skew_records,
           "helper0": lambda: helper_mesh_records()[0], "helper1": lambda: helper_mesh_records()[1], "helper2": lambda: helper_mesh_records()[2]}
 _cache = {}
+
+# ---- the mixed scene: long, short and one-triangle runs side by side in the blocks of four nodes of a level ----
+# ranges in mesh order make level 0 two blocks: {long, short, single, long} and {short, long, short-that-stays-a-leaf}
+MIXED_COUNTS = (300, 65, 1, 600, 2, 257, 40)
+MIXED_PLACES = ([-5.0, 0.5, -9.0], [0.0, 0.5, -7.0], [1.5, 2.0, -3.0], [5.0, 0.5, -9.0], [-1.5, 2.0, -3.0], [0.0, 0.5, -16.0], [0.0, 3.0, -4.0])
+
+
+def mixed_records():
+    """the seven meshes' records: random ones with distinct seeds, the last forty copies of one triangle"""
+    if "mixed" not in _cache:
+        _cache["mixed"] = [random_records(T, 900 + k) for k, T in enumerate(MIXED_COUNTS[:-1])] + [duplicate_records(MIXED_COUNTS[-1])]
+    return _cache["mixed"]
+
+
+def mixed_scene():
+    """the seven meshes, each written with the one-leaf tree and laid out "full", one instance of each in view of the camera"""
+    import compute_raytracer_amd as rt
+    from compute_raytracer_amd.scene_raytracing import TriMesh
+    soups = [soup_of(rec) for rec in mixed_records()]
+    meshes = [TriMesh(s, one_leaf_tree(s)) for s in soups]
+    models = [dict(meshIndex=k, position=list(p), eulers=[20, 30 + 40 * k, 0]) for k, p in enumerate(MIXED_PLACES)]
+    return rt.SceneRaytracing().createScene([]).createTriangleScene(meshes, models, node_capacity="full")
+
+
+def mixed_trees():
+    """build_tree of each of the seven meshes: computed once, shared by the tests, never changed"""
+    if "mixed_trees" not in _cache:
+        _cache["mixed_trees"] = [build_tree(soup_of(rec)) for rec in mixed_records()]
+    return _cache["mixed_trees"]
+
+
+def mesh_rows(scene):
+    """the ranges rebuild() passes: (root_node, node_cap, first_slot, n_slots) per mesh"""
+    ends = [m.root_node for m in scene.meshes[1:]] + [scene.node_buffer_length()]
+    return [(m.root_node, e - m.root_node, m.lookup_offset, m.soup.count) for m, e in zip(scene.meshes, ends)]
 
 
 def mesh_and_tree(name):
@@ -157,12 +205,47 @@ def leaves_of(nodes, root):
     return out, seen
 
 
+def level_widths(nodes, root):
+    """[node count per depth] under `root`, from a breadth-first walk: the widths of the levels a level-by-level build goes through"""
+    nodes = np.asarray(nodes, F).reshape(-1, 8)
+    widths, level = [], [root]
+    while level:
+        widths.append(len(level))
+        assert sum(widths) <= nodes.shape[0], "a cycle"
+        nxt = []
+        for i in level:
+            if u32f(nodes[i, 7]) == 0:
+                left = u32f(nodes[i, 3])
+                nxt += [left, left + 1]
+        level = nxt
+    return widths
+
+
 def canonical(lookup, nodes, root):
     """the lookup table with the run of every leaf under `root` sorted"""
     out = np.array(lookup, F).copy()
     for first, count in leaves_of(nodes, root)[0]:
         out[first:first + count] = np.sort(out[first:first + count])
     return out
+
+
+def check_rows_are_build_tree(nodes, lookup, before_nodes, before_lookup, rows, trees, built=None):
+    """ranges `built` (indices into rows; None: all) hold build_tree's nodes bit for bit and its order up to the order inside a
+    leaf (slot s of a mesh held triangle first_slot + s before); every other node and slot is what it was"""
+    built = range(len(rows)) if built is None else built
+    node_same, slot_same = np.ones(len(nodes), bool), np.ones(len(lookup), bool)
+    for k in built:
+        root, cap, first, n = rows[k]
+        tree = trees[k]
+        assert tree.used <= cap
+        assert np.array_equal(bits(nodes[root:root + tree.used]), bits(tree.nodes(root, first))), "mesh %d" % k
+        want = np.array(before_lookup, F).copy()
+        want[first:first + n] = (tree.order + first).astype(F)
+        assert np.array_equal(canonical(lookup, nodes, root)[first:first + n], canonical(want, nodes, root)[first:first + n]), "mesh %d" % k
+        node_same[root:root + tree.used] = False
+        slot_same[first:first + n] = False
+    assert np.array_equal(bits(nodes[node_same]), bits(np.asarray(before_nodes, F)[node_same]))      # gaps, unused capacity, the others
+    assert np.array_equal(bits(lookup[slot_same]), bits(np.asarray(before_lookup, F)[slot_same]))
 
 
 def check_well_formed(nodes, lookup, row, used, before_lookup):

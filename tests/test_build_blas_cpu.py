@@ -11,10 +11,11 @@ import pytest
 import compute_raytracer_amd as rt
 from compute_raytracer_amd import abi
 from compute_raytracer_amd.acceleration.bvh import build_tree
-from build_common import (MESHES, bits, build_host, canonical, check_well_formed, grid_records, mesh_and_tree, perturbed_grid_records,
-                          random_records, ranges_array, soup_of)
+from build_common import (MESHES, MIXED_COUNTS, bits, build_host, canonical, check_rows_are_build_tree, check_well_formed, grid_records,
+                          level_widths, mesh_and_tree, mesh_rows, mixed_scene, mixed_trees, perturbed_grid_records, random_records,
+                          ranges_array, soup_of)
 from helpers import random_sky, tri_buffers
-from refit_common import B, F, FP, H, U32, W, view_scene
+from refit_common import B, F, FP, H, U32, W, deform, view_scene
 
 
 @pytest.mark.parametrize("name", list(MESHES))
@@ -41,6 +42,58 @@ def test_the_model_is_build_tree(name):
         assert tree.used == 1 and np.array_equal(lk, lookup)     # one leaf of 40, in the order the slots had
     rc, nd2, lk2, used2 = build_host(records, lk, nd, rows)        # a second call changes no byte
     assert rc == abi.RT_OK and np.array_equal(bits(nd2), bits(nd)) and np.array_equal(bits(lk2), bits(lk)) and used2[0] == used[0]
+
+
+def test_the_skew_mesh_is_deep_and_t1000_is_wide():
+    """Input conditions of the device tests (tests/test_build_blas_gpu.py).  `skew`: a long chain of narrow levels -- one host
+    read-back, one count_up, rank_down and emit launch per level.  `T1000`: a level wider than 256 nodes with more than 256 splits
+    -- the scan's carry across its 256-node chunks already runs there and needs no further case."""
+    records, tree = mesh_and_tree("skew")
+    widths = level_widths(tree.nodes(0, 0), 0)
+    assert sum(widths) == tree.used and len(widths) >= 30
+    assert sum(1 for w in widths if w <= 4) >= len(widths) - 4
+    records, tree = mesh_and_tree("T1000")
+    widths = level_widths(tree.nodes(0, 0), 0)
+    assert sum(widths) == tree.used
+    assert any(a > 256 and b > 512 for a, b in zip(widths, widths[1:]))
+
+
+def test_run_lengths_at_the_edges_of_the_partitions():
+    """the input condition of T64 .. T513: their roots split (the partition of a run of exactly that length runs), and the two
+    sides of the comparison with kBuildShort = 256 are both there"""
+    for name, T in (("T64", 64), ("T128", 128), ("T256", 256), ("T257", 257), ("T512", 512), ("T513", 513)):
+        records, tree = mesh_and_tree(name)
+        assert records.shape[0] == T and tree.count[0] == 0 and tree.used > 1, name
+
+
+def test_the_mixed_scene_is_build_tree_per_mesh():
+    """The scene of the device's call-shape test, through the model alone: all seven ranges in one call, in mesh order and reversed,
+    equal build_tree per mesh; the unused capacity of every range and the top-level nodes stay untouched.  Then the model after a
+    deformation of mesh 0, and the input condition that its tree is another one."""
+    scene, mat = mixed_scene(), rt.Material.white()
+    buf = tri_buffers(scene, mat)
+    rows, trees = mesh_rows(scene), mixed_trees()
+    assert [r[3] for r in rows] == list(MIXED_COUNTS) and [r[1] for r in rows] == [max(2 * T - 1, 1) for T in MIXED_COUNTS]
+    assert np.array_equal(buf["tri_lookup"], np.arange(sum(MIXED_COUNTS), dtype=F))
+    assert sum(T > 256 for T in MIXED_COUNTS[:4]) == 2 and MIXED_COUNTS[2] == 1 and trees[6].used == 1      # long, short, single, long | ..., a leaf
+    assert all(t.used > 1 for t, T in zip(trees[:6], MIXED_COUNTS) if T > 1)
+    rc, nd, lk, used = build_host(buf["triangles"], buf["tri_lookup"], buf["nodes"], rows)
+    assert rc == abi.RT_OK and used.tolist() == [t.used for t in trees]
+    check_rows_are_build_tree(nd, lk, buf["nodes"], buf["tri_lookup"], rows, trees)
+    assert any(t.used < r[1] for t, r in zip(trees, rows))                                                  # there is unused capacity
+    rc, nd2, lk2, used2 = build_host(buf["triangles"], buf["tri_lookup"], buf["nodes"], rows[::-1])
+    assert rc == abi.RT_OK and used2.tolist() == used.tolist()[::-1]
+    assert np.array_equal(bits(nd2), bits(nd)) and np.array_equal(bits(lk2), bits(lk))
+    rc, nd3, lk3, used3 = build_host(buf["triangles"], buf["tri_lookup"], buf["nodes"], [rows[3], rows[0]])
+    assert rc == abi.RT_OK and used3.tolist() == [trees[3].used, trees[0].used]
+    check_rows_are_build_tree(nd3, lk3, buf["nodes"], buf["tri_lookup"], rows, trees, built=[3, 0])
+    root, cap, first, n = rows[0]
+    tris = deform(buf["triangles"], first, n, "grow")
+    moved = build_tree(soup_of(tris[first:first + n]))
+    assert moved.used != trees[0].used or not np.array_equal(bits(moved.nodes(root, first)[:, [3, 7]]), bits(trees[0].nodes(root, first)[:, [3, 7]]))
+    rc, nd4, lk4, used4 = build_host(tris, lk, nd, [rows[0]])
+    assert rc == abi.RT_OK and used4.tolist() == [moved.used]
+    check_rows_are_build_tree(nd4, lk4, nd, lk, rows, [moved] + trees[1:], built=[0])
 
 
 def two_meshes():
