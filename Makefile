@@ -7,7 +7,7 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-fast-math -Wall -Wn
 SRCS     := $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h)) include/rt355.h
 # identity of the build: profiles (profiles/traffic.json) are evidence for the sources they were taken with
 BUILD_ID := $(shell cat $(SRCS) | sha256sum | cut -c1-16)
-OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o $(CSRC)/rt_query.o $(CSRC)/rt_shade.o $(CSRC)/rt_sample.o $(CSRC)/rt_gbuffer.o $(CSRC)/rt_refit.o $(CSRC)/rt_build.o
+OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o $(CSRC)/rt_query.o $(CSRC)/rt_shade.o $(CSRC)/rt_sample.o $(CSRC)/rt_gbuffer.o $(CSRC)/rt_ao.o $(CSRC)/rt_refit.o $(CSRC)/rt_build.o
 
 all: lib oracle node
 
@@ -38,6 +38,10 @@ $(CSRC)/rt_sample.o: $(CSRC)/rt_sample.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_
 
 # geometry frames: rt_query.o's walks from the camera, stored as planes; rt_query.o's flags exactly (exactness rests on them)
 $(CSRC)/rt_gbuffer.o: $(CSRC)/rt_gbuffer.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
+
+# ambient-occlusion frames: rt_gbuffer.o's primary walk, then rt_query.o's occlusion walks from the hit; the same flags exactly
+$(CSRC)/rt_ao.o: $(CSRC)/rt_ao.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 # the BLAS refit: float32 min / max only, nothing to contract

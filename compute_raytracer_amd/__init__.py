@@ -25,12 +25,12 @@ from .material import Material
 from .soup import TriangleSoup, parse_obj
 from .acceleration import MeshTree, build_tree
 from .instances import Instances
-from .renderer_raytracing import RendererRaytracing
+from .renderer_raytracing import RendererRaytracing, ao_directions
 from . import abi, tiles
 
 __all__ = [
     "Camera", "Light", "Sphere", "SceneRaytracing", "synthetic_scene", "BASELINE_CONFIGS",
     "CubemapMaterial", "Material", "TriMesh", "load_mesh", "load_mesh_file", "TriangleSoup", "parse_obj",
     "MeshTree", "build_tree", "Instances",
-    "RendererRaytracing", "abi", "tiles",
+    "RendererRaytracing", "ao_directions", "abi", "tiles",
 ]

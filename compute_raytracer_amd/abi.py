@@ -23,6 +23,7 @@ RT_MODE_FAST = 0
 RT_MODE_STRICT = 1
 RT_QUERY_LIMITS = 1      # flags of rt_trace_rays_ex / rt_occluded: ray words 3 and 7 are tmin and tmax
 RT355_MAX_HITS = 8       # the largest k of rt_trace_rays_multi
+RT355_MAX_AO_RAYS = 64   # the largest k of rt_render_ao
 RT_SHADE_COMPOSE = 1     # flags of rt_shade_rays: r, g, b is pixelColor (RK:91-96) instead of rayColor
 RT355_MAX_SUPERSAMPLE = 4   # the largest s of rt_render_samples
 
@@ -45,6 +46,7 @@ SYMBOLS = [
     "rt_trace_rays_multi", "rt_trace_rays_multi_host",
     "rt_render_samples", "rt_render_samples_host",
     "rt_render_gbuffer", "rt_render_gbuffer_host",
+    "rt_render_ao", "rt_render_ao_host",
     "rt_update_triangles", "rt_refit_blas", "rt_read_nodes", "rt_refit_plan",
     "rt_build_blas", "rt_read_tri_lookup", "rt_build_blas_host",
 ]
@@ -103,6 +105,15 @@ class RtBlasRange(ctypes.Structure):
 
 # the same record as a numpy dtype: an (n,) array of it is what rt_build_blas takes
 BLAS_RANGE_DTYPE = [("root_node", "<u4"), ("node_cap", "<u4"), ("first_slot", "<u4"), ("n_slots", "<u4")]
+
+
+class RtAo(ctypes.Structure):
+    """rt_ao (include/rt355.h): the two planes of an ambient-occlusion frame, either of them NULL but not both; 16 bytes."""
+    _fields_ = [("count", ctypes.c_void_p), ("ao", ctypes.c_void_p)]
+
+
+# the planes of rt_ao in the struct's order: name -> (trailing shape, numpy dtype, alignment of the device form in bytes)
+AO_PLANES = {"count": ((), "u1", 1), "ao": ((), "<f4", 4)}
 
 
 class RtError(RuntimeError):
@@ -217,6 +228,8 @@ def load():
         "rt_render_samples_host": (ctypes.c_int, [vp, u32, vp, sz, vp, sz]),
         "rt_render_gbuffer": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(RtGbuffer), sz, vp]),
         "rt_render_gbuffer_host": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(RtGbuffer), sz]),
+        "rt_render_ao": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_float), u32, ctypes.c_float, ctypes.c_float, ctypes.POINTER(RtAo), sz, vp]),
+        "rt_render_ao_host": (ctypes.c_int, [vp, ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_float), u32, ctypes.c_float, ctypes.c_float, ctypes.POINTER(RtAo), sz]),
         "rt_update_triangles": (ctypes.c_int, [vp, u32, u32, fp]),
         "rt_refit_blas": (ctypes.c_int, [vp, ctypes.POINTER(u32), u32]),
         "rt_read_nodes": (ctypes.c_int, [vp, u32, u32, fp]),

@@ -2238,6 +2238,92 @@ int rt_render_gbuffer_host(rt_ctx* c, const uint32_t* rect, const rt_gbuffer* ou
     return RT_OK;
 }
 
+// ---- ambient-occlusion frames (rt_ao.hip) --------------------------------------------------------------------------------------
+
+static_assert(sizeof(rt_ao) == 16, "rt_ao is two pointers");
+
+// The checks of both forms, in the header's order: k; context, `dirs`, `out`, planes; the state; the rectangle; the capacity.
+// o: the planes as given, the rectangle the call means, and the directions and limits -- copied here, at the call.
+static int ao_check(const char* who, rt_ctx* c, const uint32_t* rect, const float* dirs, uint32_t k, float tmin, float radius, const rt_ao* out,
+                    size_t cap_pixels, bool device, RtAoOut& o) {
+    char msg[200];
+    if (k == 0u || k > RT355_MAX_AO_RAYS) { std::snprintf(msg, sizeof msg, "%s: k = %u is not in 1 .. %u", who, k, RT355_MAX_AO_RAYS); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!dirs) { std::snprintf(msg, sizeof msg, "%s: dirs is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!out) { std::snprintf(msg, sizeof msg, "%s: out is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!out->count && !out->ao) { std::snprintf(msg, sizeof msg, "%s: both planes are NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (device && reinterpret_cast<uintptr_t>(out->ao) % 4u) { std::snprintf(msg, sizeof msg, "%s: ao must be 4-byte aligned", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (!c->W || !c->H) { std::snprintf(msg, sizeof msg, "%s: rt_resize has not been called", who); return fail(RT_ERR_STATE, msg); }
+    { int rc = query_scene_written(c, who); if (rc != RT_OK) return rc; }
+    if (!c->have_params) { std::snprintf(msg, sizeof msg, "%s: rt_write_params has not been called", who); return fail(RT_ERR_STATE, msg); }
+    const uint32_t x0 = rect ? rect[0] : 0u, y0 = rect ? rect[1] : 0u, w = rect ? rect[2] : c->W, h = rect ? rect[3] : c->H;
+    if (!w || !h || (uint64_t)x0 + w > c->W || (uint64_t)y0 + h > c->H) {   // full-frame coordinates, whatever the partition
+        std::snprintf(msg, sizeof msg, "%s: the rectangle {%u, %u, %u, %u} is empty or not inside the %u x %u frame", who, x0, y0, w, h, c->W, c->H);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    if (cap_pixels < (size_t)w * h) {
+        std::snprintf(msg, sizeof msg, "%s: a %u x %u rectangle needs room for %zu pixels in every plane", who, w, h, (size_t)w * h);
+        return fail(RT_ERR_CAPACITY, msg);
+    }
+    std::memset(&o, 0, sizeof o);
+    o.count = out->count;
+    o.ao = out->ao;
+    o.x0 = x0; o.y0 = y0; o.w = w; o.h = h;
+    o.W = c->W; o.H = c->H;
+    o.k = k; o.tmin = tmin; o.radius = radius;
+    std::memcpy(o.dirs, dirs, (size_t)k * 3u * sizeof(float));
+    return RT_OK;
+}
+
+// The occlusion kernel on `s` behind query_prepare, with gbuffer_launch's camera
+static int ao_launch(rt_ctx* c, const RtAoOut& o, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+    RtFrameArgs fa;
+    std::memset(&fa, 0, sizeof fa);
+    std::memcpy(fa.p, c->params, sizeof fa.p);
+    fa.W = c->W; fa.H = c->H;
+    if (tri) RT_HIP(rt_launch_ao_triangles(fa, ts, inst, o, s));
+    else RT_HIP(rt_launch_ao_spheres(fa, c->d_records, c->n, o, s));
+    RT_HIP(hipEventRecord(c->ev_query, s));
+    c->query_pending = true;
+    c->query_last = s;
+    return RT_OK;
+}
+
+int rt_render_ao(rt_ctx* c, const uint32_t* rect, const float* dirs, uint32_t k, float tmin, float radius, const rt_ao* out, size_t cap_pixels, void* hip_stream) {
+    RtAoOut o;
+    { int rc = ao_check("rt_render_ao", c, rect, dirs, k, tmin, radius, out, cap_pixels, true, o); if (rc != RT_OK) return rc; }
+    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_render_ao", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    return ao_launch(c, o, s, tri, ts, inst);
+}
+
+int rt_render_ao_host(rt_ctx* c, const uint32_t* rect, const float* dirs, uint32_t k, float tmin, float radius, const rt_ao* out, size_t cap_pixels) {
+    RtAoOut o;
+    { int rc = ao_check("rt_render_ao_host", c, rect, dirs, k, tmin, radius, out, cap_pixels, false, o); if (rc != RT_OK) return rc; }
+    hipStream_t s;
+    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
+    bool tri;
+    int inst;
+    RtTriScene ts;
+    { int rc = query_prepare(c, "rt_render_ao_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    // (one staging buffer of the ray queries, idle between calls: the float plane first, so that it starts aligned)
+    const size_t px = (size_t)o.w * o.h;
+    const size_t b_ao = out->ao ? px * 4u : 0u, b_count = out->count ? px : 0u;
+    { int rc = grow_staging(c->d_qhits, b_ao + b_count); if (rc != RT_OK) return rc; }
+    uint8_t* const base = static_cast<uint8_t*>(c->d_qhits.p);
+    RtAoOut d = o;
+    d.ao = out->ao ? reinterpret_cast<float*>(base) : nullptr;
+    d.count = out->count ? base + b_ao : nullptr;
+    { int rc = ao_launch(c, d, s, tri, ts, inst); if (rc != RT_OK) return rc; }
+    if (out->ao) RT_HIP(hipMemcpyAsync(out->ao, d.ao, b_ao, hipMemcpyDeviceToHost, s));
+    if (out->count) RT_HIP(hipMemcpyAsync(out->count, d.count, b_count, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    return RT_OK;
+}
+
 int rt_device_pixels(rt_ctx* c, void** out_ptr, size_t* out_bytes) {
     if (!c || !out_ptr || !out_bytes) return fail(RT_ERR_INVALID_ARG, "rt_device_pixels: NULL argument");
     if (!c->d_out) return fail(RT_ERR_STATE, "rt_device_pixels: no colour buffer (rt_resize first)");

@@ -20,27 +20,6 @@
 
 namespace rtk {
 
-#ifndef RT_GBUFFER_ROWS
-constexpr uint32_t kGbufTileW = 8u * kQueryWaves, kGbufTileH = 8u;   // a workgroup's pixels: kQueryWaves 8 x 8 tiles in a row
-#else                                                                // development builds (docs/experiments.md): a wave is 64 x 1 pixels
-constexpr uint32_t kGbufTileW = kQueryThreads, kGbufTileH = 1u;
-#endif
-
-// the pixel of this lane, (x, y) within the rectangle; false: the lane has none
-__device__ __forceinline__ bool pixel_of_lane(const RtGbufferOut& O, uint32_t& x, uint32_t& y) {
-    const uint32_t cols = (O.w + kGbufTileW - 1u) / kGbufTileW;
-    const uint32_t by = blockIdx.x / cols, bx = blockIdx.x - by * cols;
-#ifndef RT_GBUFFER_ROWS
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    x = bx * kGbufTileW + wave * 8u + (lane & 7u);
-    y = by * kGbufTileH + (lane >> 3);
-#else
-    x = bx * kGbufTileW + threadIdx.x;
-    y = by;
-#endif
-    return x < O.w && y < O.h;
-}
-
 // rt_hit as planes: pixel (x, y) of the rectangle
 __device__ __forceinline__ void store_planes(const RtGbufferOut& O, uint32_t x, uint32_t y, float t, float u, float v, int prim, int inst,
                                              v3 n) {
@@ -106,13 +85,9 @@ __global__ __launch_bounds__(kQueryThreads) void gbuffer_spheres(const RtFrameAr
     store_planes(O, x, y, nearest, 0.0f, 0.0f, idx, -1, nrm);
 }
 
-static uint64_t gbuffer_blocks(const RtGbufferOut& o) {
-    return (uint64_t)((o.w + kGbufTileW - 1u) / kGbufTileW) * ((o.h + kGbufTileH - 1u) / kGbufTileH);
-}
-
 template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
 static void launch_gb(const RtFrameArgs& a, const RtTriScene& t, const RtGbufferOut& o, hipStream_t s) {
-    hipLaunchKernelGGL((gbuffer_triangles<STK, PACKED, PAIRS, P16, INST>), dim3((uint32_t)gbuffer_blocks(o)), dim3(kQueryThreads), 0, s, a, t, o);
+    hipLaunchKernelGGL((gbuffer_triangles<STK, PACKED, PAIRS, P16, INST>), dim3((uint32_t)frame_blocks(o)), dim3(kQueryThreads), 0, s, a, t, o);
 }
 template <bool INST>
 static void launch_gb_walk(const RtFrameArgs& a, const RtTriScene& t, const RtGbufferOut& o, hipStream_t s) {
@@ -126,7 +101,7 @@ static void launch_gb_walk(const RtFrameArgs& a, const RtTriScene& t, const RtGb
 // the rectangle lies in the frame the rays are made for, some plane is asked for, and the grid is one the launch can have
 static bool gbuffer_args_ok(const RtFrameArgs& a, const RtGbufferOut& o) {
     return o.W && o.H && a.W == o.W && a.H == o.H && o.w && o.h && (uint64_t)o.x0 + o.w <= o.W && (uint64_t)o.y0 + o.h <= o.H &&
-           (o.depth || o.normal || o.ids || o.uv) && rtk::gbuffer_blocks(o) <= 0x7FFFFFFFull;
+           (o.depth || o.normal || o.ids || o.uv) && rtk::frame_blocks(o) <= 0x7FFFFFFFull;
 }
 
 // the forms of rt_launch_query_triangles
@@ -142,6 +117,6 @@ hipError_t rt_launch_gbuffer_triangles(const RtFrameArgs& a, const RtTriScene& t
 
 hipError_t rt_launch_gbuffer_spheres(const RtFrameArgs& a, const float* records, uint32_t n_spheres, const RtGbufferOut& o, hipStream_t s) {
     if (!gbuffer_args_ok(a, o)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(rtk::gbuffer_spheres, dim3((uint32_t)rtk::gbuffer_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, records, n_spheres, o);
+    hipLaunchKernelGGL(rtk::gbuffer_spheres, dim3((uint32_t)rtk::frame_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, records, n_spheres, o);
     return hipGetLastError();
 }

@@ -91,4 +91,8 @@ hipError_t rt_launch_sample_spheres(const RtFrameArgs& a, const float* records, 
 // rectangle, as planes.  `a`: the camera words of a.p and a.W = o.W, a.H = o.H (nothing else of it is read).  inst as above.
 hipError_t rt_launch_gbuffer_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtGbufferOut& o, hipStream_t s);
 hipError_t rt_launch_gbuffer_spheres(const RtFrameArgs& a, const float* records, uint32_t n_spheres, const RtGbufferOut& o, hipStream_t s);
+// Ambient-occlusion frames (rt_ao.hip; include/rt355.h: rt_render_ao): per pixel of o's rectangle how many of o.k any-hit rays from
+// the primary ray's hit point are occluded.  `a` and inst as for the geometry frames.
+hipError_t rt_launch_ao_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtAoOut& o, hipStream_t s);
+hipError_t rt_launch_ao_spheres(const RtFrameArgs& a, const float* records, uint32_t n_spheres, const RtAoOut& o, hipStream_t s);
 hipError_t rt_launch_pick_rays(const RtFrameArgs& a, const uint32_t* xy, float4* rays, uint32_t n, hipStream_t s);   // xy: [n][2] u32

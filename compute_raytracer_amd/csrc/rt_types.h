@@ -94,6 +94,19 @@ struct RtGbufferOut {
     uint32_t W, H;
 };
 
+// Ambient-occlusion frames (rt_ao.hip; include/rt355.h: rt_render_ao): the planes of rt_ao as the kernels store them, each [h][w] of
+// the rectangle {x0, y0, w, h} of the W x H frame and null when not asked for (not both), and what the k rays of a pixel are made
+// from -- the directions by value, so that a kernel reads them from its own arguments through a uniform address.
+struct RtAoOut {
+    uint8_t* count;            // how many of the k rays are occluded
+    float* ao;                 // (float)(k - count) / (float)k
+    uint32_t x0, y0, w, h;
+    uint32_t W, H;
+    uint32_t k;                // 1 .. RT355_MAX_AO_RAYS
+    float tmin, radius;        // the limits of every ray, as under RT_QUERY_LIMITS
+    float dirs[3u * RT355_MAX_AO_RAYS];   // [k][3], tangent space of the shading normal (z along it)
+};
+
 struct RtLaunchCfg {
     int mode;      // rt_mode
     int variant;   // kernel variant id; 0 = default

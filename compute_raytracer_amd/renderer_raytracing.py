@@ -17,6 +17,27 @@ from .cubemap_material import CubemapMaterial
 from .scene_raytracing import CONSTANT_SKY_RGBA
 
 
+def ao_directions(k):
+    """k directions over the hemisphere z > 0 with density proportional to z (cosine-weighted), as (k, 3) float32 of unit length to
+    float32 rounding: point i of the Hammersley set ((i + 0.5) / k, the base-2 radical inverse of i) mapped through the disc
+    (Malley's method).  The same bits on every call; render_ao's default rays."""
+    k = int(k)
+    if k < 1:
+        raise ValueError("ao_directions: k must be at least 1")
+    i = np.arange(k, dtype=np.uint64)
+    u = (i.astype(np.float64) + 0.5) / k                                 # in (0, 1): z = sqrt(1 - u) > 0
+    v = np.zeros(k, np.float64)
+    bit, scale = i.copy(), 0.5
+    while bit.any():                                                     # the radical inverse: the bits of i mirrored about the point
+        v += scale * (bit & np.uint64(1)).astype(np.float64)
+        bit >>= np.uint64(1)
+        scale *= 0.5
+    r, phi = np.sqrt(u), 2.0 * np.pi * v
+    d = np.stack([r * np.cos(phi), r * np.sin(phi), np.sqrt(1.0 - u)], axis=1)
+    d /= np.sqrt((d * d).sum(axis=1))[:, None]
+    return d.astype(np.float32)
+
+
 class RendererRaytracing:
     def __init__(self, width, height, scene, device=0, maxBounces=4, rank=0, world=1):
         self.scene = scene                     # RR:54
@@ -531,6 +552,65 @@ class RendererRaytracing:
             run.wait_stream(cur)
         gb = abi.RtGbuffer(**{n: t.data_ptr() for n, t in out.items()})
         abi.check(self._lib.rt_render_gbuffer(self._ctx, c_rect, ctypes.byref(gb), w * h, ctypes.c_void_p(run.cuda_stream)), self._ctx)
+        if run is not cur:
+            cur.wait_stream(run)
+        return out
+
+    # ---- ambient-occlusion frames: k occlusion rays per pixel over the hemisphere of what the camera sees (rt_render_ao / rt_render_ao_host) ----
+    def render_ao(self, directions=None, k=16, radius=1.0, tmin=0.001, rect=None, planes=("ao",), out=None):
+        """Per pixel of the frame the next render() would show (recalculateScene() first), or of rect = (x0, y0, w, h) of it: how many
+        of k rays from the point pick() sees there are occluded() within (tmin, radius).  `directions` is (k, 3), 1 <= k <=
+        abi.RT355_MAX_AO_RAYS, in the tangent space of the shading normal (z along it), used as given; None: ao_directions(k).
+        `count` (h, w) uint8 is the number of occluded rays (0 on a miss), `ao` (h, w) float32 is (k - count) / k (1 on a miss).  The
+        rays are made on the device: no plane, ray or per-ray answer passes through memory.
+
+        numpy (out=None): a dict of the arrays named in `planes`, through rt_render_ao_host.  torch: `out` is a dict of contiguous
+        tensors of those shapes and dtypes on this renderer's device, `count` (torch.uint8), `ao` (torch.float32) or both (`planes`
+        is then not read) -> `out`, enqueued through rt_render_ao on torch.cuda.current_stream()."""
+        dirs = ao_directions(k) if directions is None else np.ascontiguousarray(directions, dtype=np.float32)
+        if dirs.ndim != 2 or dirs.shape[1] != 3 or not 1 <= dirs.shape[0] <= abi.RT355_MAX_AO_RAYS:
+            raise ValueError("render_ao: directions is (k, 3) with 1 <= k <= %d" % abi.RT355_MAX_AO_RAYS)
+        if rect is None:
+            x0, y0, w, h = 0, 0, self.width, self.height
+            c_rect = None
+        else:
+            x0, y0, w, h = (int(v) for v in rect)
+            if min(x0, y0, w, h) < 0 or max(x0, y0, w, h) > 0xFFFFFFFF:
+                raise ValueError("render_ao: rect is (x0, y0, w, h), four unsigned 32-bit numbers")
+            c_rect = (ctypes.c_uint32 * 4)(x0, y0, w, h)
+        args = (self._ctx, c_rect, dirs.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), dirs.shape[0], float(tmin), float(radius))
+        if out is not None:
+            return self._render_ao_torch(args, w, h, out)
+        names = [planes] if isinstance(planes, str) else list(planes)
+        if not names or len(set(names)) != len(names) or any(n not in abi.AO_PLANES for n in names):
+            raise ValueError("render_ao: planes is a non-empty selection of %s" % ", ".join(abi.AO_PLANES))
+        self.recalculateScene()
+        res = {n: np.zeros((h, w), abi.AO_PLANES[n][1]) for n in names}
+        ao = abi.RtAo(**{n: (a.ctypes.data if a.size else None) for n, a in res.items()})
+        abi.check(self._lib.rt_render_ao_host(*args, ctypes.byref(ao), w * h), self._ctx)
+        return res
+
+    def _render_ao_torch(self, args, w, h, out):
+        import torch
+        if not isinstance(out, dict) or not out or any(n not in abi.AO_PLANES for n in out):
+            raise ValueError("render_ao: out is a dict of tensors named %s" % ", ".join(abi.AO_PLANES))
+        for n, t in out.items():
+            want = torch.uint8 if n == "count" else torch.float32
+            if type(t).__module__.split(".")[0] != "torch" or t.dtype != want or tuple(t.shape) != (h, w) or not t.is_contiguous():
+                raise ValueError("render_ao: out[%r] must be a contiguous %s tensor of shape %r" % (n, want, (h, w)))
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("render_ao: out must live on cuda:%d, this renderer's device" % self.device)
+        self.recalculateScene()
+        dev = next(iter(out.values())).device
+        cur = torch.cuda.current_stream(dev)
+        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
+        if cur.cuda_stream == 0:
+            if getattr(self, "_query_stream", None) is None:
+                self._query_stream = torch.cuda.Stream(dev)
+            run = self._query_stream
+            run.wait_stream(cur)
+        ao = abi.RtAo(**{n: t.data_ptr() for n, t in out.items()})
+        abi.check(self._lib.rt_render_ao(*args, ctypes.byref(ao), w * h, ctypes.c_void_p(run.cuda_stream)), self._ctx)
         if run is not cur:
             cur.wait_stream(run)
         return out

@@ -477,6 +477,48 @@ typedef struct rt_gbuffer {
 int rt_render_gbuffer(rt_ctx* ctx, const uint32_t* rect, const rt_gbuffer* out, size_t cap_pixels, void* hip_stream); /* device, async */
 int rt_render_gbuffer_host(rt_ctx* ctx, const uint32_t* rect, const rt_gbuffer* out, size_t cap_pixels);             /* host, sync   */
 
+/* ---- ambient-occlusion frames: per pixel, how many of k rays over the hemisphere of what the camera sees are blocked ----------- */
+
+#define RT355_MAX_AO_RAYS 64u
+
+typedef struct rt_ao {
+    uint8_t* count;   /* [h][w]    u8 : how many of the k rays are occluded; 0 on a miss        */
+    float*   ao;      /* [h][w]    f32: (float)(k - count) / (float)k; 1.0f on a miss            */
+} rt_ao;              /* either may be NULL, not both */
+
+/* rt_render_ao / rt_render_ao_host: rt_render_gbuffer's depth and normal planes, k rays per pixel made from them and rt_occluded over
+ * those rays, in one kernel that keeps a pixel's hit point and tangent frame in registers -- no plane, no ray and no per-ray answer
+ * in memory.  Device form: the planes in device memory of this context's GPU (ao 4-byte aligned), enqueued on `hip_stream` (NULL =
+ * the context's stream), returns at once.  Host form: host memory, synchronous, staged through query buffers the context owns.
+ *
+ * rect and cap_pixels are rt_render_gbuffer's: {x0, y0, w, h} in full-frame pixels of the last rt_resize whatever the partition, NULL
+ * the whole frame, read at the call; the planes are [h][w] of the rectangle, row 0 at the top, and cap_pixels is the room of every
+ * non-NULL plane in pixels.  dirs is HOST memory in both forms: k directions, [k][3] f32, in the tangent space of the shading
+ * normal (z along the normal).  It is copied at the call -- a later change to the array does not reach an enqueued call.  Nothing
+ * normalises or checks the directions.  (tmin, radius) are the limits of every ray, exactly as under RT_QUERY_LIMITS; NaN limits or
+ * tmin >= radius are not errors: every ray is then a miss and every count 0.
+ *
+ * A pixel, in float32 without fused multiply-add, one operation per line, in this order:
+ *   h = the rt_hit that rt_pick returns for the pixel; on a miss count = 0, ao = 1.0f and nothing else is done;
+ *   p = o + h.t * d per component (one multiply, one add: HK:319), o the camera origin and d the pixel's primary direction;
+ *   n = h.normal;  s = (n.z >= 0) ? 1 : -1  (so -0 gives +1 and NaN gives -1);  a = -1 / (s + n.z);  b = (n.x * n.y) * a;
+ *   T = (1 + ((s * n.x) * n.x) * a,  s * b,  (-s) * n.x);   B = (b,  s + (n.y * n.y) * a,  -n.y);
+ *   ray j: origin p, direction (dirs[j].x * T + dirs[j].y * B) + dirs[j].z * n per component, limits (tmin, radius);
+ *   count = the number of j for which rt_occluded (RT_QUERY_LIMITS) reports 1 for that ray -- the same walk taking the same steps,
+ *   back faces culled as there; sphere scenes use the literal loop for the primary ray and the k rays, the normal from HK:320.
+ * No sky, mesh texture, light or maxBounces is read.
+ *
+ * Contract.  That of rt_render_gbuffer, word for word: sees every write made before it; takes no slot of the event ring, changes no
+ * field of rt_stats, has no rt_kernel_id; is unaffected by rt_select_kernel, rt_set_mode and rt_set_variant; never disturbs frames
+ * in flight; queries run in call order, and scene writes after one wait for it.
+ *
+ * Checks, in this order: k == 0 or k > RT355_MAX_AO_RAYS: RT_ERR_INVALID_ARG.  Then a NULL context, NULL `dirs`, NULL `out`, both
+ * planes NULL, or in the device form an `ao` plane that is not 4-byte aligned: RT_ERR_INVALID_ARG.  Then RT_ERR_STATE: no rt_resize,
+ * no scene written, or no rt_write_params.  Then the rectangle, as for rt_render_gbuffer: RT_ERR_INVALID_ARG.  Then
+ * cap_pixels < w * h: RT_ERR_CAPACITY. */
+int rt_render_ao(rt_ctx* ctx, const uint32_t* rect, const float* dirs, uint32_t k, float tmin, float radius, const rt_ao* out, size_t cap_pixels, void* hip_stream); /* device, async */
+int rt_render_ao_host(rt_ctx* ctx, const uint32_t* rect, const float* dirs, uint32_t k, float tmin, float radius, const rt_ao* out, size_t cap_pixels);             /* host, sync   */
+
 /* ---- multi-GPU: render + RCCL gather behind one call (RR:434-470 across a group of GPUs) ------ */
 
 /* One process per GPU.  Rank 0 calls rt_comm_unique_id and hands the bytes to the other ranks by
