@@ -25,23 +25,23 @@ $(CSRC)/rt_triangles.o: $(CSRC)/rt_triangles.hip $(CSRC)/rt_tri_device.h $(CSRC)
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 # ray queries: the triangle kernel's traversal and the literal sphere test, the same flags (exactness rests on them)
-$(CSRC)/rt_query.o: $(CSRC)/rt_query.hip $(CSRC)/rt_query_device.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
+$(CSRC)/rt_query.o: $(CSRC)/rt_query.hip $(CSRC)/rt_query_device.h $(CSRC)/rt_query_form.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 # shaded ray queries: the frame kernels' bounce loop over caller rays, rt_query.o's flags exactly (exactness rests on them)
-$(CSRC)/rt_shade.o: $(CSRC)/rt_shade.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
+$(CSRC)/rt_shade.o: $(CSRC)/rt_shade.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_query_form.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 # supersampled frames: rt_shade.o's bounce loops from the camera, resolved on the chip; rt_shade.o's flags exactly
-$(CSRC)/rt_sample.o: $(CSRC)/rt_sample.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
+$(CSRC)/rt_sample.o: $(CSRC)/rt_sample.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_query_form.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 # geometry frames: rt_query.o's walks from the camera, stored as planes; rt_query.o's flags exactly (exactness rests on them)
-$(CSRC)/rt_gbuffer.o: $(CSRC)/rt_gbuffer.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
+$(CSRC)/rt_gbuffer.o: $(CSRC)/rt_gbuffer.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_query_form.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 # ambient-occlusion frames: rt_gbuffer.o's primary walk, then rt_query.o's occlusion walks from the hit; the same flags exactly
-$(CSRC)/rt_ao.o: $(CSRC)/rt_ao.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
+$(CSRC)/rt_ao.o: $(CSRC)/rt_ao.hip $(CSRC)/rt_shade_device.h $(CSRC)/rt_query_device.h $(CSRC)/rt_query_form.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_filter.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 # the BLAS refit: float32 min / max only, nothing to contract

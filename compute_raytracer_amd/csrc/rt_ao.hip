@@ -139,17 +139,6 @@ __global__ __launch_bounds__(kQueryThreads) void ao_spheres(const RtFrameArgs A,
     if (live) store_ao(O, x, y, count);
 }
 
-template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-static void launch_ao(const RtFrameArgs& a, const RtTriScene& t, const RtAoOut& o, hipStream_t s) {
-    hipLaunchKernelGGL((ao_triangles<STK, PACKED, PAIRS, P16, INST>), dim3((uint32_t)frame_blocks(o)), dim3(kQueryThreads), 0, s, a, t, o);
-}
-template <bool INST>
-static void launch_ao_walk(const RtFrameArgs& a, const RtTriScene& t, const RtAoOut& o, hipStream_t s) {
-    if (t.n_nodes <= 65536u && t.packed_ok) launch_ao<uint16_t, true, false, false, INST>(a, t, o, s);
-    else if (t.n_nodes <= 65536u)          launch_ao<uint16_t, false, false, false, INST>(a, t, o, s);
-    else                                   launch_ao<uint32_t, false, false, false, INST>(a, t, o, s);
-}
-
 }  // namespace rtk
 
 // the three argument blocks of ao_triangles travel by value: together they must fit the 4 KB a kernel's arguments may take
@@ -161,14 +150,13 @@ static bool ao_args_ok(const RtFrameArgs& a, const RtAoOut& o) {
            (o.count || o.ao) && o.k >= 1u && o.k <= RT355_MAX_AO_RAYS && rtk::frame_blocks(o) <= 0x7FFFFFFFull;
 }
 
-// the forms of rt_launch_gbuffer_triangles, which are rt_launch_limited_triangles' too: a ray is walked in the form rt_occluded walks it in
+// (one form for the primary walk and the k occlusion walks: a ray is walked in the form rt_occluded walks it in)
 hipError_t rt_launch_ao_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtAoOut& o, hipStream_t s) {
     if (!ao_args_ok(a, o)) return hipErrorInvalidValue;
-    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= rtk::kWideBlas;
-    if (pairs && t.p16_ok) rtk::launch_ao<uint16_t, true, true, true, true>(a, t, o, s);
-    else if (pairs)        rtk::launch_ao<uint16_t, true, true, false, true>(a, t, o, s);
-    else if (inst)         rtk::launch_ao_walk<true>(a, t, o, s);
-    else                   rtk::launch_ao_walk<false>(a, t, o, s);
+    rtk::query_form(t, inst, [&](auto f) {
+        typedef decltype(f) F;
+        hipLaunchKernelGGL((rtk::ao_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3((uint32_t)rtk::frame_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, t, o);
+    });
     return hipGetLastError();
 }
 

@@ -762,6 +762,16 @@ static int apply_version(rt_ctx* c, uint32_t v, uint32_t slot, hipStream_t s) {
     return RT_OK;
 }
 
+// What a kernel may assume of the sky, for frames (rt_enqueue) and shaded queries (shade_frame_args).  flat: six 1x1 faces of one
+// colour.  seamless: six equal squares -- what WebGPU accepts as a cube texture (CM:35-79: 512 x 512 x 6).
+static void sky_flags(const rt_ctx* c, uint32_t& flat, uint32_t& seamless) {
+    flat = seamless = 1u;
+    for (int i = 0; i < 6; ++i) {
+        if (c->fw[i] != 1u || c->fh[i] != 1u || c->face_texel0[i] != c->face_texel0[0]) flat = 0u;
+        if (c->fw[i] != c->fw[0] || c->fh[i] != c->fw[0]) seamless = 0u;
+    }
+}
+
 int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     if (!c->W || !c->H) return fail(RT_ERR_STATE, "rt_render: rt_resize has not been called");
     if (!c->have_params) return fail(RT_ERR_STATE, "rt_render: rt_write_params has not been called");
@@ -825,9 +835,8 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
         return fail(RT_ERR_UNSUPPORTED, buf);
     }
     if (queue_pipeline) { int rc = ensure_queue(c); if (rc != RT_OK) return rc; }
-    bool sky_flat = true;       // six 1x1 faces of one colour
-    for (int i = 0; i < 6; ++i)
-        if (c->fw[i] != 1u || c->fh[i] != 1u || c->face_texel0[i] != c->face_texel0[0]) sky_flat = false;
+    uint32_t sky_flat, sky_seamless;
+    sky_flags(c, sky_flat, sky_seamless);
     const bool resolve_pass = use_bvh && !sky_flat;      // rt_bvh.hip: sky_resolve
     if (resolve_pass) { int rc = ensure_fin(c); if (rc != RT_OK) return rc; }
     // The hierarchy after rt_write_spheres.  A changed sphere count (or the first frame): host build, here and
@@ -992,10 +1001,8 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     unsigned long long* counters = c->d_rays + (kCtrlBytes / 8u) * slot;
     unsigned long long* ctrl = counters + kCounterBytes / 8u;
     for (int i = 0; i < 6; ++i) { fa.face[i] = c->d_face[i]; fa.fw[i] = c->fw[i]; fa.fh[i] = c->fh[i]; }
-    fa.sky_flat = sky_flat ? 1u : 0u;
-    fa.sky_seamless = 1u;   // six equal squares: what WebGPU accepts as a cube texture (CM:35-79: 512 x 512 x 6)
-    for (int i = 0; i < 6; ++i)
-        if (c->fw[i] != c->fw[0] || c->fh[i] != c->fw[0]) fa.sky_seamless = 0u;
+    fa.sky_flat = sky_flat;
+    fa.sky_seamless = sky_seamless;
     fa.out = dst;
     // one record buffer per frame that may be running: the frame kStreams slots back must be through with this one
     fa.fin = resolve_pass ? c->d_fin[slot % (uint32_t)kStreams] : nullptr;
@@ -1793,21 +1800,43 @@ static int query_prepare(rt_ctx* c, const char* who, hipStream_t s, bool& tri, R
     return RT_OK;
 }
 
-// flags (RT_QUERY_LIMITS) or `any` (rt_occluded: `out` is one byte per ray): the limited forms; otherwise rt_trace_rays' own
-static int query_launch(rt_ctx* c, const float4* rays, void* out, uint32_t n, hipStream_t s, bool tri, const RtTriScene& ts, int inst,
-                        uint32_t flags = 0u, bool any = false) {
-    if (!flags && !any) {
-        float4* hits = static_cast<float4*>(out);
-        if (tri) RT_HIP(rt_launch_query_triangles(ts, inst, rays, hits, n, s));
-        else RT_HIP(rt_launch_query_spheres(c->d_records, c->n, rays, hits, n, s));
+extern "C++" {     // (templates below)
+
+// A query between query_open and query_close: the stream it runs on and what it reads there
+struct Query {
+    hipStream_t s;
+    bool tri;
+    int inst;
+    RtTriScene ts;
+};
+
+// Opens a query: its stream, and query_prepare on it.  Results in device memory: `hip_stream`, or the context's own when that is
+// NULL.  The host-memory forms (host): the context's query stream, made at its first use.
+static int query_open(rt_ctx* c, const char* who, bool host, void* hip_stream, Query& q) {
+    if (host) {
+        RT_HIP(hipSetDevice(c->device));
+        if (!c->query_stream) RT_HIP(hipStreamCreateWithFlags(&c->query_stream, hipStreamNonBlocking));
+        q.s = c->query_stream;
     } else {
-        if (tri) RT_HIP(rt_launch_limited_triangles(ts, inst, rays, flags, any, out, n, s));
-        else RT_HIP(rt_launch_limited_spheres(c->d_records, c->n, rays, flags, any, out, n, s));
+        q.s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     }
-    RT_HIP(hipEventRecord(c->ev_query, s));
+    return query_prepare(c, who, q.s, q.tri, q.ts, q.inst);
+}
+// Closes it behind the kernels launched on q.s: what the next query on another stream, and rt_drain, wait for
+static int query_close(rt_ctx* c, const Query& q) {
+    RT_HIP(hipEventRecord(c->ev_query, q.s));
     c->query_pending = true;
-    c->query_last = s;
+    c->query_last = q.s;
     return RT_OK;
+}
+
+// A query with its results in device memory: launch(q) between open and close
+template <typename LAUNCH>
+static int query_run(rt_ctx* c, const char* who, void* hip_stream, LAUNCH launch) {
+    Query q;
+    { int rc = query_open(c, who, false, hip_stream, q); if (rc != RT_OK) return rc; }
+    { int rc = launch(q); if (rc != RT_OK) return rc; }
+    return query_close(c, q);
 }
 
 // a staging buffer of the host-memory queries (synchronous: idle between calls): grows, contents not kept
@@ -1821,57 +1850,102 @@ static int grow_staging(rt_ctx::DevBuf& b, size_t need) {
     return RT_OK;
 }
 
-static int query_stream(rt_ctx* c, hipStream_t& s) {
-    RT_HIP(hipSetDevice(c->device));
-    if (!c->query_stream) RT_HIP(hipStreamCreateWithFlags(&c->query_stream, hipStreamNonBlocking));
-    s = c->query_stream;
+// One result of a host-memory query: `bytes` from the staging buffer `buf` to `host` (NULL: not asked for).  Results that share a
+// buffer stand together in the list and lie in the buffer one after the other, in the list's order.  dev: where, once staged.
+struct Staged {
+    void* host;
+    rt_ctx::DevBuf* buf;
+    size_t bytes;
+    uint8_t* dev;
+};
+
+// A query with its results in host memory, synchronous, through the context's staging buffers: grow them, copy `in` (the rays or
+// pixels of the call; NULL: none) to in_buf, launch(q) between open and close, copy every result back, wait.
+template <size_t N, typename LAUNCH>
+static int query_run_host(rt_ctx* c, const char* who, const void* in, rt_ctx::DevBuf* in_buf, size_t in_bytes, Staged (&out)[N], LAUNCH launch) {
+    Query q;
+    { int rc = query_open(c, who, true, nullptr, q); if (rc != RT_OK) return rc; }
+    if (in) { int rc = grow_staging(*in_buf, in_bytes); if (rc != RT_OK) return rc; }
+    size_t at[N], end = 0u;
+    for (size_t i = 0; i < N; ++i) {
+        if (i && out[i].buf != out[i - 1u].buf) end = 0u;
+        at[i] = end;
+        if (out[i].host) end += out[i].bytes;
+        if (i + 1u == N || out[i + 1u].buf != out[i].buf) { int rc = grow_staging(*out[i].buf, end); if (rc != RT_OK) return rc; }
+    }
+    for (size_t i = 0; i < N; ++i) out[i].dev = out[i].host ? static_cast<uint8_t*>(out[i].buf->p) + at[i] : nullptr;
+    if (in) RT_HIP(hipMemcpyAsync(in_buf->p, in, in_bytes, hipMemcpyHostToDevice, q.s));
+    { int rc = launch(q); if (rc != RT_OK) return rc; }
+    { int rc = query_close(c, q); if (rc != RT_OK) return rc; }
+    for (size_t i = 0; i < N; ++i)
+        if (out[i].host) RT_HIP(hipMemcpyAsync(out[i].host, out[i].dev, out[i].bytes, hipMemcpyDeviceToHost, q.s));
+    RT_HIP(hipStreamSynchronize(q.s));
     return RT_OK;
+}
+
+}  // extern "C++"
+
+// The checks every ray-array query starts with, in the header's order: the flags against `allowed` (a pure argument check,
+// whatever the context); k, in the call that has one (NULL: none); the context; n == 0 (*done: nothing to do); the pointers; and
+// for device memory the alignment `aligned` names in the message -- 16 bytes for `rays`, out_align for `out` (1: a byte per ray).
+// aligned NULL: host memory, any address.
+static int rays_check(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, uint32_t allowed, const uint32_t* k,
+                      const void* out, const char* aligned, uint32_t out_align, bool& done) {
+    char msg[160];
+    done = false;
+    if (flags & ~allowed) { std::snprintf(msg, sizeof msg, "%s: unknown flag bits 0x%x", who, flags); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (k && (*k == 0u || *k > RT355_MAX_HITS)) {
+        std::snprintf(msg, sizeof msg, "%s: k = %u is outside 1 .. RT355_MAX_HITS (%u)", who, *k, RT355_MAX_HITS);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (n == 0) { done = true; return RT_OK; }
+    if (!rays || !out) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (aligned && (reinterpret_cast<uintptr_t>(rays) % 16u || reinterpret_cast<uintptr_t>(out) % out_align)) {
+        std::snprintf(msg, sizeof msg, "%s: %s must be 16-byte aligned", who, aligned);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    return RT_OK;
+}
+
+// The camera of the last rt_write_params in a kernel's arguments, for a frame of W x H; everything else zero
+static void camera_frame_args(const rt_ctx* c, uint32_t W, uint32_t H, RtFrameArgs& fa) {
+    std::memset(&fa, 0, sizeof fa);
+    std::memcpy(fa.p, c->params, sizeof fa.p);
+    fa.W = W; fa.H = H;
 }
 
 static_assert(sizeof(rt_hit) == 32, "rt_hit is two float4");
 
+// flags (RT_QUERY_LIMITS) or `any` (rt_occluded: `out` is one byte per ray): the limited forms; otherwise rt_trace_rays' own
+static int query_launch(rt_ctx* c, const float4* rays, void* out, uint32_t n, const Query& q, uint32_t flags = 0u, bool any = false) {
+    if (!flags && !any) {
+        float4* hits = static_cast<float4*>(out);
+        if (q.tri) RT_HIP(rt_launch_query_triangles(q.ts, q.inst, rays, hits, n, q.s));
+        else RT_HIP(rt_launch_query_spheres(c->d_records, c->n, rays, hits, n, q.s));
+    } else {
+        if (q.tri) RT_HIP(rt_launch_limited_triangles(q.ts, q.inst, rays, flags, any, out, n, q.s));
+        else RT_HIP(rt_launch_limited_spheres(c->d_records, c->n, rays, flags, any, out, n, q.s));
+    }
+    return RT_OK;
+}
+
 // rt_trace_rays_ex / rt_occluded: device memory, on `hip_stream`; `out` holds n rt_hit records, or n bytes when `any`
 static int query_device(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, bool any, void* out, void* hip_stream) {
-    char msg[160];
-    // (the flags first: a pure argument check, whatever the context)
-    if (flags & ~RT_QUERY_LIMITS) { std::snprintf(msg, sizeof msg, "%s: unknown flag bits 0x%x", who, flags); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (n == 0) return RT_OK;
-    if (!rays || !out) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
-    if ((reinterpret_cast<uintptr_t>(rays) | (any ? (uintptr_t)0 : reinterpret_cast<uintptr_t>(out))) % 16u) {
-        std::snprintf(msg, sizeof msg, "%s: %s must be 16-byte aligned", who, any ? "rays" : "rays and hits");
-        return fail(RT_ERR_INVALID_ARG, msg);
-    }
-    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, who, s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    return query_launch(c, reinterpret_cast<const float4*>(rays), out, n, s, tri, ts, inst, flags, any);
+    bool done;
+    { int rc = rays_check(who, c, rays, n, flags, RT_QUERY_LIMITS, nullptr, out, any ? "rays" : "rays and hits", any ? 1u : 16u, done);
+      if (rc != RT_OK || done) return rc; }
+    return query_run(c, who, hip_stream, [&](const Query& q) { return query_launch(c, reinterpret_cast<const float4*>(rays), out, n, q, flags, any); });
 }
 
 // rt_trace_rays_host_ex / rt_occluded_host: host memory, staged through the context's query buffers, synchronous
 static int query_host(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, bool any, void* out) {
-    char msg[160];
-    // (the flags first: a pure argument check, whatever the context)
-    if (flags & ~RT_QUERY_LIMITS) { std::snprintf(msg, sizeof msg, "%s: unknown flag bits 0x%x", who, flags); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (n == 0) return RT_OK;
-    if (!rays || !out) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
-    hipStream_t s;
-    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, who, s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    const size_t bytes = (size_t)n * 32u, out_bytes = any ? (size_t)n : bytes;
-    { int rc = grow_staging(c->d_qrays, bytes); if (rc != RT_OK) return rc; }
-    { int rc = grow_staging(c->d_qhits, out_bytes); if (rc != RT_OK) return rc; }
-    RT_HIP(hipMemcpyAsync(c->d_qrays.p, rays, bytes, hipMemcpyHostToDevice, s));
-    { int rc = query_launch(c, static_cast<const float4*>(c->d_qrays.p), c->d_qhits.p, n, s, tri, ts, inst, flags, any); if (rc != RT_OK) return rc; }
-    RT_HIP(hipMemcpyAsync(out, c->d_qhits.p, out_bytes, hipMemcpyDeviceToHost, s));
-    RT_HIP(hipStreamSynchronize(s));
-    return RT_OK;
+    bool done;
+    { int rc = rays_check(who, c, rays, n, flags, RT_QUERY_LIMITS, nullptr, out, nullptr, 1u, done); if (rc != RT_OK || done) return rc; }
+    Staged r[] = {{out, &c->d_qhits, any ? (size_t)n : (size_t)n * 32u}};
+    return query_run_host(c, who, rays, &c->d_qrays, (size_t)n * 32u, r, [&](const Query& q) {
+        return query_launch(c, static_cast<const float4*>(c->d_qrays.p), r[0].dev, n, q, flags, any);
+    });
 }
 
 int rt_trace_rays_ex(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, rt_hit* hits, void* hip_stream) {
@@ -1900,61 +1974,30 @@ int rt_trace_rays_host(rt_ctx* c, const float* rays, uint32_t n, rt_hit* hits) {
 // The argument checks of both forms, in the header's order: flags, k, context, n == 0 (*done), pointers
 static int multi_check(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, uint32_t k, const rt_hit* hits, bool device,
                        bool& done) {
-    char msg[160];
-    done = false;
-    if (flags & ~RT_QUERY_LIMITS) { std::snprintf(msg, sizeof msg, "%s: unknown flag bits 0x%x", who, flags); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (k == 0u || k > RT355_MAX_HITS) {
-        std::snprintf(msg, sizeof msg, "%s: k = %u is outside 1 .. RT355_MAX_HITS (%u)", who, k, RT355_MAX_HITS);
-        return fail(RT_ERR_INVALID_ARG, msg);
-    }
-    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (n == 0) { done = true; return RT_OK; }
-    if (!rays || !hits) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (device && (reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(hits)) % 16u) {
-        std::snprintf(msg, sizeof msg, "%s: rays and hits must be 16-byte aligned", who);
-        return fail(RT_ERR_INVALID_ARG, msg);
-    }
-    return RT_OK;
+    return rays_check(who, c, rays, n, flags, RT_QUERY_LIMITS, &k, hits, device ? "rays and hits" : nullptr, 16u, done);
 }
 
-static int multi_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flags, uint32_t k, float4* hits, hipStream_t s, bool tri,
-                        const RtTriScene& ts, int inst) {
-    if (tri) RT_HIP(rt_launch_multi_triangles(ts, inst, rays, flags, k, hits, n, s));
-    else RT_HIP(rt_launch_multi_spheres(c->d_records, c->n, rays, flags, k, hits, n, s));
-    RT_HIP(hipEventRecord(c->ev_query, s));
-    c->query_pending = true;
-    c->query_last = s;
+static int multi_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flags, uint32_t k, float4* hits, const Query& q) {
+    if (q.tri) RT_HIP(rt_launch_multi_triangles(q.ts, q.inst, rays, flags, k, hits, n, q.s));
+    else RT_HIP(rt_launch_multi_spheres(c->d_records, c->n, rays, flags, k, hits, n, q.s));
     return RT_OK;
 }
 
 int rt_trace_rays_multi(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, uint32_t k, rt_hit* hits, void* hip_stream) {
     bool done;
     { int rc = multi_check("rt_trace_rays_multi", c, rays, n, flags, k, hits, true, done); if (rc != RT_OK || done) return rc; }
-    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_trace_rays_multi", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    return multi_launch(c, reinterpret_cast<const float4*>(rays), n, flags, k, reinterpret_cast<float4*>(hits), s, tri, ts, inst);
+    return query_run(c, "rt_trace_rays_multi", hip_stream, [&](const Query& q) {
+        return multi_launch(c, reinterpret_cast<const float4*>(rays), n, flags, k, reinterpret_cast<float4*>(hits), q);
+    });
 }
 
 int rt_trace_rays_multi_host(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, uint32_t k, rt_hit* hits) {
     bool done;
     { int rc = multi_check("rt_trace_rays_multi_host", c, rays, n, flags, k, hits, false, done); if (rc != RT_OK || done) return rc; }
-    hipStream_t s;
-    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_trace_rays_multi_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    const size_t bytes = (size_t)n * 32u, out_bytes = bytes * k;
-    { int rc = grow_staging(c->d_qrays, bytes); if (rc != RT_OK) return rc; }
-    { int rc = grow_staging(c->d_qhits, out_bytes); if (rc != RT_OK) return rc; }
-    RT_HIP(hipMemcpyAsync(c->d_qrays.p, rays, bytes, hipMemcpyHostToDevice, s));
-    { int rc = multi_launch(c, static_cast<const float4*>(c->d_qrays.p), n, flags, k, static_cast<float4*>(c->d_qhits.p), s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    RT_HIP(hipMemcpyAsync(hits, c->d_qhits.p, out_bytes, hipMemcpyDeviceToHost, s));
-    RT_HIP(hipStreamSynchronize(s));
-    return RT_OK;
+    Staged r[] = {{hits, &c->d_qhits, (size_t)n * 32u * k}};
+    return query_run_host(c, "rt_trace_rays_multi_host", rays, &c->d_qrays, (size_t)n * 32u, r, [&](const Query& q) {
+        return multi_launch(c, static_cast<const float4*>(c->d_qrays.p), n, flags, k, reinterpret_cast<float4*>(r[0].dev), q);
+    });
 }
 
 int rt_pick(rt_ctx* c, const uint32_t* xy, uint32_t n, rt_hit* hits) {
@@ -1965,26 +2008,15 @@ int rt_pick(rt_ctx* c, const uint32_t* xy, uint32_t n, rt_hit* hits) {
     if (!c->have_params) return fail(RT_ERR_STATE, "rt_pick: rt_write_params has not been called");
     for (uint32_t i = 0; i < n; ++i)          // full-frame coordinates, whatever the partition
         if (xy[2u * i] >= c->W || xy[2u * i + 1u] >= c->H) return fail(RT_ERR_INVALID_ARG, "rt_pick: pixel outside the frame");
-    hipStream_t s;
-    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_pick", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    const size_t bytes = (size_t)n * 32u;
-    { int rc = grow_staging(c->d_qxy, (size_t)n * 8u); if (rc != RT_OK) return rc; }
-    { int rc = grow_staging(c->d_qrays, bytes); if (rc != RT_OK) return rc; }
-    { int rc = grow_staging(c->d_qhits, bytes); if (rc != RT_OK) return rc; }
-    RT_HIP(hipMemcpyAsync(c->d_qxy.p, xy, (size_t)n * 8u, hipMemcpyHostToDevice, s));
-    RtFrameArgs fa;
-    std::memset(&fa, 0, sizeof fa);
-    std::memcpy(fa.p, c->params, sizeof fa.p);
-    fa.W = c->W; fa.H = c->H;
-    RT_HIP(rt_launch_pick_rays(fa, static_cast<const uint32_t*>(c->d_qxy.p), static_cast<float4*>(c->d_qrays.p), n, s));
-    { int rc = query_launch(c, static_cast<const float4*>(c->d_qrays.p), static_cast<float4*>(c->d_qhits.p), n, s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    RT_HIP(hipMemcpyAsync(hits, c->d_qhits.p, bytes, hipMemcpyDeviceToHost, s));
-    RT_HIP(hipStreamSynchronize(s));
-    return RT_OK;
+    Staged r[] = {{hits, &c->d_qhits, (size_t)n * 32u}};
+    return query_run_host(c, "rt_pick", xy, &c->d_qxy, (size_t)n * 8u, r, [&](const Query& q) {
+        // the pixels' primary rays, made on the device into the ray queries' own staging buffer, then rt_trace_rays' kernel
+        { int rc = grow_staging(c->d_qrays, (size_t)n * 32u); if (rc != RT_OK) return rc; }
+        RtFrameArgs fa;
+        camera_frame_args(c, c->W, c->H, fa);
+        RT_HIP(rt_launch_pick_rays(fa, static_cast<const uint32_t*>(c->d_qxy.p), static_cast<float4*>(c->d_qrays.p), n, q.s));
+        return query_launch(c, static_cast<const float4*>(c->d_qrays.p), r[0].dev, n, q);
+    });
 }
 
 // ---- shaded ray queries (rt_shade.hip) -----------------------------------------------------------------------------------------
@@ -2007,72 +2039,42 @@ static int shade_state(const char* who, rt_ctx* c) {
 
 // The argument checks of both forms, in query_device's order: flags, context, n == 0 (*done), pointers; then shade_state.
 static int shade_check(const char* who, rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, const rt_shade* out, bool device, bool& done) {
-    char msg[160];
-    done = false;
-    // (the flags first: a pure argument check, whatever the context)
-    if (flags & ~RT_SHADE_COMPOSE) { std::snprintf(msg, sizeof msg, "%s: unknown flag bits 0x%x", who, flags); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (n == 0) { done = true; return RT_OK; }
-    if (!rays || !out) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (device && (reinterpret_cast<uintptr_t>(rays) | reinterpret_cast<uintptr_t>(out)) % 16u) {
-        std::snprintf(msg, sizeof msg, "%s: rays and out must be 16-byte aligned", who);
-        return fail(RT_ERR_INVALID_ARG, msg);
-    }
+    { int rc = rays_check(who, c, rays, n, flags, RT_SHADE_COMPOSE, nullptr, out, device ? "rays and out" : nullptr, 16u, done);
+      if (rc != RT_OK || done) return rc; }
     return shade_state(who, c);
 }
 
-// The shade kernel on `s` behind query_prepare: parameters, cube faces and sky flags as rt_enqueue assembles them for a frame,
-// by value in the kernel's arguments -- no slot of the event ring, no counters, no field of the stats.
-static void shade_frame_args(const rt_ctx* c, RtFrameArgs& fa) {
-    std::memset(&fa, 0, sizeof fa);
-    std::memcpy(fa.p, c->params, sizeof fa.p);
-    fa.sky_flat = 1u;           // six 1x1 faces of one colour
-    fa.sky_seamless = 1u;       // six equal squares
-    for (int i = 0; i < 6; ++i) {
-        fa.face[i] = c->d_face[i]; fa.fw[i] = c->fw[i]; fa.fh[i] = c->fh[i];
-        if (c->fw[i] != 1u || c->fh[i] != 1u || c->face_texel0[i] != c->face_texel0[0]) fa.sky_flat = 0u;
-        if (c->fw[i] != c->fw[0] || c->fh[i] != c->fw[0]) fa.sky_seamless = 0u;
-    }
+// A shade kernel's arguments for a target of W x H: parameters, cube faces and sky flags as rt_enqueue assembles them for a frame,
+// by value -- no slot of the event ring, no counters, no field of the stats.
+static void shade_frame_args(const rt_ctx* c, uint32_t W, uint32_t H, RtFrameArgs& fa) {
+    camera_frame_args(c, W, H, fa);
+    for (int i = 0; i < 6; ++i) { fa.face[i] = c->d_face[i]; fa.fw[i] = c->fw[i]; fa.fh[i] = c->fh[i]; }
+    sky_flags(c, fa.sky_flat, fa.sky_seamless);
 }
-static int shade_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flags, float4* out, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+// The shade kernel on q.s behind query_prepare (rays have no frame: W = H = 0)
+static int shade_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flags, float4* out, const Query& q) {
     RtFrameArgs fa;
-    shade_frame_args(c, fa);
-    if (tri) RT_HIP(rt_launch_shade_triangles(fa, ts, inst, rays, flags, out, n, s));
-    else RT_HIP(rt_launch_shade_spheres(fa, c->d_records, c->n, rays, flags, out, n, s));
-    RT_HIP(hipEventRecord(c->ev_query, s));
-    c->query_pending = true;
-    c->query_last = s;
+    shade_frame_args(c, 0u, 0u, fa);
+    if (q.tri) RT_HIP(rt_launch_shade_triangles(fa, q.ts, q.inst, rays, flags, out, n, q.s));
+    else RT_HIP(rt_launch_shade_spheres(fa, c->d_records, c->n, rays, flags, out, n, q.s));
     return RT_OK;
 }
 
 int rt_shade_rays(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, rt_shade* out, void* hip_stream) {
     bool done;
     { int rc = shade_check("rt_shade_rays", c, rays, n, flags, out, true, done); if (rc != RT_OK || done) return rc; }
-    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_shade_rays", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    return shade_launch(c, reinterpret_cast<const float4*>(rays), n, flags, reinterpret_cast<float4*>(out), s, tri, ts, inst);
+    return query_run(c, "rt_shade_rays", hip_stream, [&](const Query& q) {
+        return shade_launch(c, reinterpret_cast<const float4*>(rays), n, flags, reinterpret_cast<float4*>(out), q);
+    });
 }
 
 int rt_shade_rays_host(rt_ctx* c, const float* rays, uint32_t n, uint32_t flags, rt_shade* out) {
     bool done;
     { int rc = shade_check("rt_shade_rays_host", c, rays, n, flags, out, false, done); if (rc != RT_OK || done) return rc; }
-    hipStream_t s;
-    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_shade_rays_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    const size_t bytes = (size_t)n * 32u, out_bytes = (size_t)n * sizeof(rt_shade);
-    { int rc = grow_staging(c->d_qrays, bytes); if (rc != RT_OK) return rc; }
-    { int rc = grow_staging(c->d_qhits, out_bytes); if (rc != RT_OK) return rc; }
-    RT_HIP(hipMemcpyAsync(c->d_qrays.p, rays, bytes, hipMemcpyHostToDevice, s));
-    { int rc = shade_launch(c, static_cast<const float4*>(c->d_qrays.p), n, flags, static_cast<float4*>(c->d_qhits.p), s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    RT_HIP(hipMemcpyAsync(out, c->d_qhits.p, out_bytes, hipMemcpyDeviceToHost, s));
-    RT_HIP(hipStreamSynchronize(s));
-    return RT_OK;
+    Staged r[] = {{out, &c->d_qhits, (size_t)n * sizeof(rt_shade)}};
+    return query_run_host(c, "rt_shade_rays_host", rays, &c->d_qrays, (size_t)n * 32u, r, [&](const Query& q) {
+        return shade_launch(c, static_cast<const float4*>(c->d_qrays.p), n, flags, reinterpret_cast<float4*>(r[0].dev), q);
+    });
 }
 
 // ---- supersampled frames (rt_sample.hip) ---------------------------------------------------------------------------------------
@@ -2101,52 +2103,57 @@ static int sample_check(const char* who, rt_ctx* c, uint32_t s, const uint8_t* r
     return RT_OK;
 }
 
-// The sample kernel on `s` behind query_prepare: shade_launch's arguments with the camera of the last rt_write_params and the
+// The sample kernel on q.s behind query_prepare: shade_launch's arguments with the camera of the last rt_write_params and the
 // target the samples are pixels of, s W x s H -- the whole frame, whatever the partition
-static int sample_launch(rt_ctx* c, uint32_t ss, uint8_t* rgba8, float* rgbaf, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+static int sample_launch(rt_ctx* c, uint32_t ss, uint8_t* rgba8, float* rgbaf, const Query& q) {
     RtFrameArgs fa;
-    shade_frame_args(c, fa);
-    fa.W = ss * c->W; fa.H = ss * c->H;
+    shade_frame_args(c, ss * c->W, ss * c->H, fa);
     const RtSampleOut o = {c->W, c->H, ss, reinterpret_cast<uint32_t*>(rgba8), reinterpret_cast<float4*>(rgbaf)};
-    if (tri) RT_HIP(rt_launch_sample_triangles(fa, ts, inst, o, s));
-    else RT_HIP(rt_launch_sample_spheres(fa, c->d_records, c->n, o, s));
-    RT_HIP(hipEventRecord(c->ev_query, s));
-    c->query_pending = true;
-    c->query_last = s;
+    if (q.tri) RT_HIP(rt_launch_sample_triangles(fa, q.ts, q.inst, o, q.s));
+    else RT_HIP(rt_launch_sample_spheres(fa, c->d_records, c->n, o, q.s));
     return RT_OK;
 }
 
 int rt_render_samples(rt_ctx* c, uint32_t ss, uint8_t* rgba8, size_t cap8, float* rgbaf, size_t capf, void* hip_stream) {
     { int rc = sample_check("rt_render_samples", c, ss, rgba8, cap8, rgbaf, capf, true); if (rc != RT_OK) return rc; }
-    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_render_samples", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    return sample_launch(c, ss, rgba8, rgbaf, s, tri, ts, inst);
+    return query_run(c, "rt_render_samples", hip_stream, [&](const Query& q) { return sample_launch(c, ss, rgba8, rgbaf, q); });
 }
 
 int rt_render_samples_host(rt_ctx* c, uint32_t ss, uint8_t* rgba8, size_t cap8, float* rgbaf, size_t capf) {
     { int rc = sample_check("rt_render_samples_host", c, ss, rgba8, cap8, rgbaf, capf, false); if (rc != RT_OK) return rc; }
-    hipStream_t s;
-    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_render_samples_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
     // (the staging buffers of the ray queries, idle between calls: the bytes where their rays go, the floats where their results go)
     const size_t px = (size_t)c->W * c->H;
-    if (rgba8) { int rc = grow_staging(c->d_qrays, px * 4u); if (rc != RT_OK) return rc; }
-    if (rgbaf) { int rc = grow_staging(c->d_qhits, px * 16u); if (rc != RT_OK) return rc; }
-    { int rc = sample_launch(c, ss, rgba8 ? static_cast<uint8_t*>(c->d_qrays.p) : nullptr, rgbaf ? static_cast<float*>(c->d_qhits.p) : nullptr, s, tri, ts, inst);
-      if (rc != RT_OK) return rc; }
-    if (rgba8) RT_HIP(hipMemcpyAsync(rgba8, c->d_qrays.p, px * 4u, hipMemcpyDeviceToHost, s));
-    if (rgbaf) RT_HIP(hipMemcpyAsync(rgbaf, c->d_qhits.p, px * 16u, hipMemcpyDeviceToHost, s));
-    RT_HIP(hipStreamSynchronize(s));
-    return RT_OK;
+    Staged r[] = {{rgba8, &c->d_qrays, px * 4u}, {rgbaf, &c->d_qhits, px * 16u}};
+    return query_run_host(c, "rt_render_samples_host", nullptr, nullptr, 0u, r, [&](const Query& q) {
+        return sample_launch(c, ss, r[0].dev, reinterpret_cast<float*>(r[1].dev), q);
+    });
 }
 
-// ---- geometry frames (rt_gbuffer.hip) ------------------------------------------------------------------------------------------
+// ---- the frame-shaped queries: geometry frames (rt_gbuffer.hip) and ambient-occlusion frames (rt_ao.hip) --------------------------
+
+// What both check after their own arguments, in the header's order: the state (rt_resize, a scene, rt_write_params), the rectangle
+// (NULL: the whole frame), the capacity.  o.{x0, y0, w, h}: the rectangle the call means; o.{W, H}: the frame it lies in.
+extern "C++" {
+template <typename OUT>
+static int frame_query_check(const char* who, rt_ctx* c, const uint32_t* rect, size_t cap_pixels, OUT& o) {
+    char msg[200];
+    if (!c->W || !c->H) { std::snprintf(msg, sizeof msg, "%s: rt_resize has not been called", who); return fail(RT_ERR_STATE, msg); }
+    { int rc = query_scene_written(c, who); if (rc != RT_OK) return rc; }
+    if (!c->have_params) { std::snprintf(msg, sizeof msg, "%s: rt_write_params has not been called", who); return fail(RT_ERR_STATE, msg); }
+    const uint32_t x0 = rect ? rect[0] : 0u, y0 = rect ? rect[1] : 0u, w = rect ? rect[2] : c->W, h = rect ? rect[3] : c->H;
+    if (!w || !h || (uint64_t)x0 + w > c->W || (uint64_t)y0 + h > c->H) {   // full-frame coordinates, whatever the partition
+        std::snprintf(msg, sizeof msg, "%s: the rectangle {%u, %u, %u, %u} is empty or not inside the %u x %u frame", who, x0, y0, w, h, c->W, c->H);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    if (cap_pixels < (size_t)w * h) {
+        std::snprintf(msg, sizeof msg, "%s: a %u x %u rectangle needs room for %zu pixels in every plane", who, w, h, (size_t)w * h);
+        return fail(RT_ERR_CAPACITY, msg);
+    }
+    o.x0 = x0; o.y0 = y0; o.w = w; o.h = h;
+    o.W = c->W; o.H = c->H;
+    return RT_OK;
+}
+}  // extern "C++"
 
 static_assert(sizeof(rt_gbuffer) == 32, "rt_gbuffer is four pointers");
 
@@ -2162,83 +2169,45 @@ static int gbuffer_check(const char* who, rt_ctx* c, const uint32_t* rect, const
         std::snprintf(msg, sizeof msg, "%s: depth must be 4-byte, ids and uv 8-byte and normal 16-byte aligned", who);
         return fail(RT_ERR_INVALID_ARG, msg);
     }
-    if (!c->W || !c->H) { std::snprintf(msg, sizeof msg, "%s: rt_resize has not been called", who); return fail(RT_ERR_STATE, msg); }
-    { int rc = query_scene_written(c, who); if (rc != RT_OK) return rc; }
-    if (!c->have_params) { std::snprintf(msg, sizeof msg, "%s: rt_write_params has not been called", who); return fail(RT_ERR_STATE, msg); }
-    const uint32_t x0 = rect ? rect[0] : 0u, y0 = rect ? rect[1] : 0u, w = rect ? rect[2] : c->W, h = rect ? rect[3] : c->H;
-    if (!w || !h || (uint64_t)x0 + w > c->W || (uint64_t)y0 + h > c->H) {   // full-frame coordinates, whatever the partition
-        std::snprintf(msg, sizeof msg, "%s: the rectangle {%u, %u, %u, %u} is empty or not inside the %u x %u frame", who, x0, y0, w, h, c->W, c->H);
-        return fail(RT_ERR_INVALID_ARG, msg);
-    }
-    if (cap_pixels < (size_t)w * h) {
-        std::snprintf(msg, sizeof msg, "%s: a %u x %u rectangle needs room for %zu pixels in every plane", who, w, h, (size_t)w * h);
-        return fail(RT_ERR_CAPACITY, msg);
-    }
     o.depth = out->depth;
     o.normal = reinterpret_cast<float4*>(out->normal);
     o.ids = reinterpret_cast<int2*>(out->ids);
     o.uv = reinterpret_cast<float2*>(out->uv);
-    o.x0 = x0; o.y0 = y0; o.w = w; o.h = h;
-    o.W = c->W; o.H = c->H;
-    return RT_OK;
+    return frame_query_check(who, c, rect, cap_pixels, o);
 }
 
-// The geometry kernel on `s` behind query_prepare: the camera of the last rt_write_params, by value in the kernel's arguments, and
+// The geometry kernel on q.s behind query_prepare: the camera of the last rt_write_params, by value in the kernel's arguments, and
 // the whole frame's size, whatever the partition -- rt_pick's ray, made in the lane
-static int gbuffer_launch(rt_ctx* c, const RtGbufferOut& o, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+static int gbuffer_launch(rt_ctx* c, const RtGbufferOut& o, const Query& q) {
     RtFrameArgs fa;
-    std::memset(&fa, 0, sizeof fa);
-    std::memcpy(fa.p, c->params, sizeof fa.p);
-    fa.W = c->W; fa.H = c->H;
-    if (tri) RT_HIP(rt_launch_gbuffer_triangles(fa, ts, inst, o, s));
-    else RT_HIP(rt_launch_gbuffer_spheres(fa, c->d_records, c->n, o, s));
-    RT_HIP(hipEventRecord(c->ev_query, s));
-    c->query_pending = true;
-    c->query_last = s;
+    camera_frame_args(c, c->W, c->H, fa);
+    if (q.tri) RT_HIP(rt_launch_gbuffer_triangles(fa, q.ts, q.inst, o, q.s));
+    else RT_HIP(rt_launch_gbuffer_spheres(fa, c->d_records, c->n, o, q.s));
     return RT_OK;
 }
 
 int rt_render_gbuffer(rt_ctx* c, const uint32_t* rect, const rt_gbuffer* out, size_t cap_pixels, void* hip_stream) {
     RtGbufferOut o;
     { int rc = gbuffer_check("rt_render_gbuffer", c, rect, out, cap_pixels, true, o); if (rc != RT_OK) return rc; }
-    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_render_gbuffer", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    return gbuffer_launch(c, o, s, tri, ts, inst);
+    return query_run(c, "rt_render_gbuffer", hip_stream, [&](const Query& q) { return gbuffer_launch(c, o, q); });
 }
 
 int rt_render_gbuffer_host(rt_ctx* c, const uint32_t* rect, const rt_gbuffer* out, size_t cap_pixels) {
     RtGbufferOut o;
     { int rc = gbuffer_check("rt_render_gbuffer_host", c, rect, out, cap_pixels, false, o); if (rc != RT_OK) return rc; }
-    hipStream_t s;
-    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_render_gbuffer_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
     // (one staging buffer of the ray queries, idle between calls, holds the planes asked for one after the other, the widest
     // first: every plane then starts on a multiple of its own alignment)
     const size_t px = (size_t)o.w * o.h;
-    const size_t b_normal = out->normal ? px * 16u : 0u, b_ids = out->ids ? px * 8u : 0u, b_uv = out->uv ? px * 8u : 0u, b_depth = out->depth ? px * 4u : 0u;
-    { int rc = grow_staging(c->d_qhits, b_normal + b_ids + b_uv + b_depth); if (rc != RT_OK) return rc; }
-    uint8_t* const base = static_cast<uint8_t*>(c->d_qhits.p);
-    RtGbufferOut d = o;
-    d.normal = out->normal ? reinterpret_cast<float4*>(base) : nullptr;
-    d.ids = out->ids ? reinterpret_cast<int2*>(base + b_normal) : nullptr;
-    d.uv = out->uv ? reinterpret_cast<float2*>(base + b_normal + b_ids) : nullptr;
-    d.depth = out->depth ? reinterpret_cast<float*>(base + b_normal + b_ids + b_uv) : nullptr;
-    { int rc = gbuffer_launch(c, d, s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    if (out->normal) RT_HIP(hipMemcpyAsync(out->normal, d.normal, b_normal, hipMemcpyDeviceToHost, s));
-    if (out->ids) RT_HIP(hipMemcpyAsync(out->ids, d.ids, b_ids, hipMemcpyDeviceToHost, s));
-    if (out->uv) RT_HIP(hipMemcpyAsync(out->uv, d.uv, b_uv, hipMemcpyDeviceToHost, s));
-    if (out->depth) RT_HIP(hipMemcpyAsync(out->depth, d.depth, b_depth, hipMemcpyDeviceToHost, s));
-    RT_HIP(hipStreamSynchronize(s));
-    return RT_OK;
+    Staged r[] = {{out->normal, &c->d_qhits, px * 16u}, {out->ids, &c->d_qhits, px * 8u}, {out->uv, &c->d_qhits, px * 8u}, {out->depth, &c->d_qhits, px * 4u}};
+    return query_run_host(c, "rt_render_gbuffer_host", nullptr, nullptr, 0u, r, [&](const Query& q) {
+        RtGbufferOut d = o;
+        d.normal = reinterpret_cast<float4*>(r[0].dev);
+        d.ids = reinterpret_cast<int2*>(r[1].dev);
+        d.uv = reinterpret_cast<float2*>(r[2].dev);
+        d.depth = reinterpret_cast<float*>(r[3].dev);
+        return gbuffer_launch(c, d, q);
+    });
 }
-
-// ---- ambient-occlusion frames (rt_ao.hip) --------------------------------------------------------------------------------------
 
 static_assert(sizeof(rt_ao) == 16, "rt_ao is two pointers");
 
@@ -2253,75 +2222,41 @@ static int ao_check(const char* who, rt_ctx* c, const uint32_t* rect, const floa
     if (!out) { std::snprintf(msg, sizeof msg, "%s: out is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
     if (!out->count && !out->ao) { std::snprintf(msg, sizeof msg, "%s: both planes are NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
     if (device && reinterpret_cast<uintptr_t>(out->ao) % 4u) { std::snprintf(msg, sizeof msg, "%s: ao must be 4-byte aligned", who); return fail(RT_ERR_INVALID_ARG, msg); }
-    if (!c->W || !c->H) { std::snprintf(msg, sizeof msg, "%s: rt_resize has not been called", who); return fail(RT_ERR_STATE, msg); }
-    { int rc = query_scene_written(c, who); if (rc != RT_OK) return rc; }
-    if (!c->have_params) { std::snprintf(msg, sizeof msg, "%s: rt_write_params has not been called", who); return fail(RT_ERR_STATE, msg); }
-    const uint32_t x0 = rect ? rect[0] : 0u, y0 = rect ? rect[1] : 0u, w = rect ? rect[2] : c->W, h = rect ? rect[3] : c->H;
-    if (!w || !h || (uint64_t)x0 + w > c->W || (uint64_t)y0 + h > c->H) {   // full-frame coordinates, whatever the partition
-        std::snprintf(msg, sizeof msg, "%s: the rectangle {%u, %u, %u, %u} is empty or not inside the %u x %u frame", who, x0, y0, w, h, c->W, c->H);
-        return fail(RT_ERR_INVALID_ARG, msg);
-    }
-    if (cap_pixels < (size_t)w * h) {
-        std::snprintf(msg, sizeof msg, "%s: a %u x %u rectangle needs room for %zu pixels in every plane", who, w, h, (size_t)w * h);
-        return fail(RT_ERR_CAPACITY, msg);
-    }
     std::memset(&o, 0, sizeof o);
     o.count = out->count;
     o.ao = out->ao;
-    o.x0 = x0; o.y0 = y0; o.w = w; o.h = h;
-    o.W = c->W; o.H = c->H;
     o.k = k; o.tmin = tmin; o.radius = radius;
     std::memcpy(o.dirs, dirs, (size_t)k * 3u * sizeof(float));
-    return RT_OK;
+    return frame_query_check(who, c, rect, cap_pixels, o);
 }
 
-// The occlusion kernel on `s` behind query_prepare, with gbuffer_launch's camera
-static int ao_launch(rt_ctx* c, const RtAoOut& o, hipStream_t s, bool tri, const RtTriScene& ts, int inst) {
+// The occlusion kernel on q.s behind query_prepare, with gbuffer_launch's camera
+static int ao_launch(rt_ctx* c, const RtAoOut& o, const Query& q) {
     RtFrameArgs fa;
-    std::memset(&fa, 0, sizeof fa);
-    std::memcpy(fa.p, c->params, sizeof fa.p);
-    fa.W = c->W; fa.H = c->H;
-    if (tri) RT_HIP(rt_launch_ao_triangles(fa, ts, inst, o, s));
-    else RT_HIP(rt_launch_ao_spheres(fa, c->d_records, c->n, o, s));
-    RT_HIP(hipEventRecord(c->ev_query, s));
-    c->query_pending = true;
-    c->query_last = s;
+    camera_frame_args(c, c->W, c->H, fa);
+    if (q.tri) RT_HIP(rt_launch_ao_triangles(fa, q.ts, q.inst, o, q.s));
+    else RT_HIP(rt_launch_ao_spheres(fa, c->d_records, c->n, o, q.s));
     return RT_OK;
 }
 
 int rt_render_ao(rt_ctx* c, const uint32_t* rect, const float* dirs, uint32_t k, float tmin, float radius, const rt_ao* out, size_t cap_pixels, void* hip_stream) {
     RtAoOut o;
     { int rc = ao_check("rt_render_ao", c, rect, dirs, k, tmin, radius, out, cap_pixels, true, o); if (rc != RT_OK) return rc; }
-    const hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_render_ao", s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    return ao_launch(c, o, s, tri, ts, inst);
+    return query_run(c, "rt_render_ao", hip_stream, [&](const Query& q) { return ao_launch(c, o, q); });
 }
 
 int rt_render_ao_host(rt_ctx* c, const uint32_t* rect, const float* dirs, uint32_t k, float tmin, float radius, const rt_ao* out, size_t cap_pixels) {
     RtAoOut o;
     { int rc = ao_check("rt_render_ao_host", c, rect, dirs, k, tmin, radius, out, cap_pixels, false, o); if (rc != RT_OK) return rc; }
-    hipStream_t s;
-    { int rc = query_stream(c, s); if (rc != RT_OK) return rc; }
-    bool tri;
-    int inst;
-    RtTriScene ts;
-    { int rc = query_prepare(c, "rt_render_ao_host", s, tri, ts, inst); if (rc != RT_OK) return rc; }
     // (one staging buffer of the ray queries, idle between calls: the float plane first, so that it starts aligned)
     const size_t px = (size_t)o.w * o.h;
-    const size_t b_ao = out->ao ? px * 4u : 0u, b_count = out->count ? px : 0u;
-    { int rc = grow_staging(c->d_qhits, b_ao + b_count); if (rc != RT_OK) return rc; }
-    uint8_t* const base = static_cast<uint8_t*>(c->d_qhits.p);
-    RtAoOut d = o;
-    d.ao = out->ao ? reinterpret_cast<float*>(base) : nullptr;
-    d.count = out->count ? base + b_ao : nullptr;
-    { int rc = ao_launch(c, d, s, tri, ts, inst); if (rc != RT_OK) return rc; }
-    if (out->ao) RT_HIP(hipMemcpyAsync(out->ao, d.ao, b_ao, hipMemcpyDeviceToHost, s));
-    if (out->count) RT_HIP(hipMemcpyAsync(out->count, d.count, b_count, hipMemcpyDeviceToHost, s));
-    RT_HIP(hipStreamSynchronize(s));
-    return RT_OK;
+    Staged r[] = {{out->ao, &c->d_qhits, px * 4u}, {out->count, &c->d_qhits, px}};
+    return query_run_host(c, "rt_render_ao_host", nullptr, nullptr, 0u, r, [&](const Query& q) {
+        RtAoOut d = o;
+        d.ao = reinterpret_cast<float*>(r[0].dev);
+        d.count = r[1].dev;
+        return ao_launch(c, d, q);
+    });
 }
 
 int rt_device_pixels(rt_ctx* c, void** out_ptr, size_t* out_bytes) {

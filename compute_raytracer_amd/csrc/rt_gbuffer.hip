@@ -85,17 +85,6 @@ __global__ __launch_bounds__(kQueryThreads) void gbuffer_spheres(const RtFrameAr
     store_planes(O, x, y, nearest, 0.0f, 0.0f, idx, -1, nrm);
 }
 
-template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-static void launch_gb(const RtFrameArgs& a, const RtTriScene& t, const RtGbufferOut& o, hipStream_t s) {
-    hipLaunchKernelGGL((gbuffer_triangles<STK, PACKED, PAIRS, P16, INST>), dim3((uint32_t)frame_blocks(o)), dim3(kQueryThreads), 0, s, a, t, o);
-}
-template <bool INST>
-static void launch_gb_walk(const RtFrameArgs& a, const RtTriScene& t, const RtGbufferOut& o, hipStream_t s) {
-    if (t.n_nodes <= 65536u && t.packed_ok) launch_gb<uint16_t, true, false, false, INST>(a, t, o, s);
-    else if (t.n_nodes <= 65536u)          launch_gb<uint16_t, false, false, false, INST>(a, t, o, s);
-    else                                   launch_gb<uint32_t, false, false, false, INST>(a, t, o, s);
-}
-
 }  // namespace rtk
 
 // the rectangle lies in the frame the rays are made for, some plane is asked for, and the grid is one the launch can have
@@ -104,14 +93,12 @@ static bool gbuffer_args_ok(const RtFrameArgs& a, const RtGbufferOut& o) {
            (o.depth || o.normal || o.ids || o.uv) && rtk::frame_blocks(o) <= 0x7FFFFFFFull;
 }
 
-// the forms of rt_launch_query_triangles
 hipError_t rt_launch_gbuffer_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtGbufferOut& o, hipStream_t s) {
     if (!gbuffer_args_ok(a, o)) return hipErrorInvalidValue;
-    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= rtk::kWideBlas;
-    if (pairs && t.p16_ok) rtk::launch_gb<uint16_t, true, true, true, true>(a, t, o, s);
-    else if (pairs)        rtk::launch_gb<uint16_t, true, true, false, true>(a, t, o, s);
-    else if (inst)         rtk::launch_gb_walk<true>(a, t, o, s);
-    else                   rtk::launch_gb_walk<false>(a, t, o, s);
+    rtk::query_form(t, inst, [&](auto f) {
+        typedef decltype(f) F;
+        hipLaunchKernelGGL((rtk::gbuffer_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3((uint32_t)rtk::frame_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, t, o);
+    });
     return hipGetLastError();
 }
 

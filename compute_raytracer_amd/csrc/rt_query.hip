@@ -329,69 +329,21 @@ __global__ __launch_bounds__(256) void pick_rays(const RtFrameArgs A, const uint
     rays[2u * i + 1u] = make_float4(d.x, d.y, d.z, 0.0f);
 }
 
-template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-static void launch_qt(const RtTriScene& t, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
-    const uint32_t blocks = (uint32_t)(((size_t)n + kQueryThreads - 1u) / kQueryThreads);
-    hipLaunchKernelGGL((query_triangles<STK, PACKED, PAIRS, P16, INST>), dim3(blocks), dim3(kQueryThreads), 0, s, t, rays, hits, n);
-}
-template <bool INST>
-static void launch_qt_walk(const RtTriScene& t, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
-    if (t.n_nodes <= 65536u && t.packed_ok) launch_qt<uint16_t, true, false, false, INST>(t, rays, hits, n, s);
-    else if (t.n_nodes <= 65536u)          launch_qt<uint16_t, false, false, false, INST>(t, rays, hits, n, s);
-    else                                   launch_qt<uint32_t, false, false, false, INST>(t, rays, hits, n, s);
-}
-
-template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST, bool ANY>
-static void launch_lt(const RtTriScene& t, const float4* rays, uint32_t flags, void* out, uint32_t n, hipStream_t s) {
-    const uint32_t blocks = (uint32_t)(((size_t)n + kQueryThreads - 1u) / kQueryThreads);
-    hipLaunchKernelGGL((limited_triangles<STK, PACKED, PAIRS, P16, INST, ANY>), dim3(blocks), dim3(kQueryThreads), 0, s, t, rays, flags,
-                       ANY ? nullptr : static_cast<float4*>(out), ANY ? static_cast<uint8_t*>(out) : nullptr, n);
-}
-template <bool INST, bool ANY>
-static void launch_lt_walk(const RtTriScene& t, const float4* rays, uint32_t flags, void* out, uint32_t n, hipStream_t s) {
-    if (t.n_nodes <= 65536u && t.packed_ok) launch_lt<uint16_t, true, false, false, INST, ANY>(t, rays, flags, out, n, s);
-    else if (t.n_nodes <= 65536u)          launch_lt<uint16_t, false, false, false, INST, ANY>(t, rays, flags, out, n, s);
-    else                                   launch_lt<uint32_t, false, false, false, INST, ANY>(t, rays, flags, out, n, s);
-}
-// the forms of rt_launch_query_triangles
-template <bool ANY>
-static void launch_lt_form(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, void* out, uint32_t n, hipStream_t s) {
-    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= kWideBlas;
-    if (pairs && t.p16_ok) launch_lt<uint16_t, true, true, true, true, ANY>(t, rays, flags, out, n, s);
-    else if (pairs)        launch_lt<uint16_t, true, true, false, true, ANY>(t, rays, flags, out, n, s);
-    else if (inst)         launch_lt_walk<true, ANY>(t, rays, flags, out, n, s);
-    else                   launch_lt_walk<false, ANY>(t, rays, flags, out, n, s);
-}
-
-template <int K, typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-static void launch_mt(const RtTriScene& t, const float4* rays, uint32_t flags, uint32_t k, float4* hits, uint32_t n, hipStream_t s) {
-    const uint32_t blocks = (uint32_t)(((size_t)n + kQueryThreads - 1u) / kQueryThreads);
-    hipLaunchKernelGGL((multi_triangles<K, STK, PACKED, PAIRS, P16, INST>), dim3(blocks), dim3(kQueryThreads), 0, s, t, rays, flags, k, hits, n);
-}
-template <int K, bool INST>
-static void launch_mt_walk(const RtTriScene& t, const float4* rays, uint32_t flags, uint32_t k, float4* hits, uint32_t n, hipStream_t s) {
-    if (t.n_nodes <= 65536u && t.packed_ok) launch_mt<K, uint16_t, true, false, false, INST>(t, rays, flags, k, hits, n, s);
-    else if (t.n_nodes <= 65536u)          launch_mt<K, uint16_t, false, false, false, INST>(t, rays, flags, k, hits, n, s);
-    else                                   launch_mt<K, uint32_t, false, false, false, INST>(t, rays, flags, k, hits, n, s);
-}
-// the forms of launch_lt_form
-template <int K>
-static void launch_mt_form(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, uint32_t k, float4* hits, uint32_t n, hipStream_t s) {
-    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= kWideBlas;
-    if (pairs && t.p16_ok) launch_mt<K, uint16_t, true, true, true, true>(t, rays, flags, k, hits, n, s);
-    else if (pairs)        launch_mt<K, uint16_t, true, true, false, true>(t, rays, flags, k, hits, n, s);
-    else if (inst)         launch_mt_walk<K, true>(t, rays, flags, k, hits, n, s);
-    else                   launch_mt_walk<K, false>(t, rays, flags, k, hits, n, s);
-}
-
 }  // namespace rtk
 
 hipError_t rt_launch_multi_triangles(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, uint32_t k, float4* hits,
                                      uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     if (k == 0 || k > RT355_MAX_HITS) return hipErrorInvalidValue;
-    if (k <= 4u) rtk::launch_mt_form<4>(t, inst, rays, flags, k, hits, n, s);
-    else         rtk::launch_mt_form<8>(t, inst, rays, flags, k, hits, n, s);
+    const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
+    // K, the capacity of a lane's list, is the outer choice; the scene's form the inner one
+    const auto launch = [&](auto f, auto cap) {
+        typedef decltype(f) F;
+        hipLaunchKernelGGL((rtk::multi_triangles<decltype(cap)::value, typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(blocks),
+                           dim3(rtk::kQueryThreads), 0, s, t, rays, flags, k, hits, n);
+    };
+    if (k <= 4u) rtk::query_form(t, inst, [&](auto f) { launch(f, std::integral_constant<int, 4>()); });
+    else         rtk::query_form(t, inst, [&](auto f) { launch(f, std::integral_constant<int, 8>()); });
     return hipGetLastError();
 }
 
@@ -407,12 +359,11 @@ hipError_t rt_launch_multi_spheres(const float* records, uint32_t n_spheres, con
 
 hipError_t rt_launch_query_triangles(const RtTriScene& t, int inst, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    // the relinked pair records: only with every instance staged (the root's meta rides in its record), as in the frame kernels
-    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= rtk::kWideBlas;
-    if (pairs && t.p16_ok) rtk::launch_qt<uint16_t, true, true, true, true>(t, rays, hits, n, s);
-    else if (pairs)        rtk::launch_qt<uint16_t, true, true, false, true>(t, rays, hits, n, s);
-    else if (inst)         rtk::launch_qt_walk<true>(t, rays, hits, n, s);
-    else                   rtk::launch_qt_walk<false>(t, rays, hits, n, s);
+    const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
+    rtk::query_form(t, inst, [&](auto f) {
+        typedef decltype(f) F;
+        hipLaunchKernelGGL((rtk::query_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(blocks), dim3(rtk::kQueryThreads), 0, s, t, rays, hits, n);
+    });
     return hipGetLastError();
 }
 
@@ -426,8 +377,16 @@ hipError_t rt_launch_query_spheres(const float* records, uint32_t n_spheres, con
 hipError_t rt_launch_limited_triangles(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, bool any, void* out,
                                        uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    if (any) rtk::launch_lt_form<true>(t, inst, rays, flags, out, n, s);
-    else     rtk::launch_lt_form<false>(t, inst, rays, flags, out, n, s);
+    const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
+    // ANY is the outer choice, the scene's form the inner one
+    const auto launch = [&](auto f, auto any_form) {
+        typedef decltype(f) F;
+        constexpr bool ANY = decltype(any_form)::value;
+        hipLaunchKernelGGL((rtk::limited_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST, ANY>), dim3(blocks), dim3(rtk::kQueryThreads),
+                           0, s, t, rays, flags, ANY ? nullptr : static_cast<float4*>(out), ANY ? static_cast<uint8_t*>(out) : nullptr, n);
+    };
+    if (any) rtk::query_form(t, inst, [&](auto f) { launch(f, std::true_type()); });
+    else     rtk::query_form(t, inst, [&](auto f) { launch(f, std::false_type()); });
     return hipGetLastError();
 }
 

@@ -1,7 +1,10 @@
 // rt_query_device.h -- what the query kernels of rt_query.hip, rt_shade.hip, rt_gbuffer.hip and rt_ao.hip share: the workgroup shape,
-// the size of a staged sphere chunk, the ray record, and the pixel of a lane in the frame-shaped queries.
+// the size of a staged sphere chunk, the ray record, the pixel of a lane in the frame-shaped queries, and the form a triangle scene's
+// kernel runs in.
 #pragma once
 #include "rt_device.h"
+#include "rt_tri_device.h"
+#include "rt_query_form.h"
 
 namespace rtk {
 
@@ -42,6 +45,13 @@ __device__ __forceinline__ bool pixel_of_lane(const OUT& O, uint32_t& x, uint32_
 template <typename OUT>
 inline uint64_t frame_blocks(const OUT& o) {
     return (uint64_t)((o.w + kGbufTileW - 1u) / kGbufTileW) * ((o.h + kGbufTileH - 1u) / kGbufTileH);
+}
+
+// f(RtQueryForm<STK, PACKED, PAIRS, P16, INST>()) for the form the scene `t` is queried in (rt_query_form.h holds the rule); inst:
+// the instance data travels in t.inst
+template <typename F>
+inline void query_form(const RtTriScene& t, int inst, F&& f) {
+    rt_query_form(inst != 0, t.pairs != nullptr, t.n_nodes, t.packed_ok != 0u, t.p16_ok != 0u, t.n_blas, kWideBlas, f);
 }
 
 }  // namespace rtk

@@ -104,31 +104,18 @@ static uint32_t sample_blocks(const RtSampleOut& o) {
     return (uint32_t)(((uint64_t)o.W * o.H + P - 1u) / P);
 }
 
-template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-static void launch_sm(const RtFrameArgs& a, const RtTriScene& t, const RtSampleOut& o, hipStream_t s) {
-    hipLaunchKernelGGL((sample_triangles<STK, PACKED, PAIRS, P16, INST>), dim3(sample_blocks(o)), dim3(kQueryThreads), 0, s, a, t, o);
-}
-template <bool INST>
-static void launch_sm_walk(const RtFrameArgs& a, const RtTriScene& t, const RtSampleOut& o, hipStream_t s) {
-    if (t.n_nodes <= 65536u && t.packed_ok) launch_sm<uint16_t, true, false, false, INST>(a, t, o, s);
-    else if (t.n_nodes <= 65536u)          launch_sm<uint16_t, false, false, false, INST>(a, t, o, s);
-    else                                   launch_sm<uint32_t, false, false, false, INST>(a, t, o, s);
-}
-
 }  // namespace rtk
 
 static bool sample_args_ok(const RtFrameArgs& a, const RtSampleOut& o) {
     return o.s >= 1u && o.s <= RT355_MAX_SUPERSAMPLE && o.W && o.H && a.W == o.s * o.W && a.H == o.s * o.H && (o.rgba8 || o.rgbaf);
 }
 
-// the forms of rt_launch_shade_triangles
 hipError_t rt_launch_sample_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtSampleOut& o, hipStream_t s) {
     if (!sample_args_ok(a, o)) return hipErrorInvalidValue;
-    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= rtk::kWideBlas;
-    if (pairs && t.p16_ok) rtk::launch_sm<uint16_t, true, true, true, true>(a, t, o, s);
-    else if (pairs)        rtk::launch_sm<uint16_t, true, true, false, true>(a, t, o, s);
-    else if (inst)         rtk::launch_sm_walk<true>(a, t, o, s);
-    else                   rtk::launch_sm_walk<false>(a, t, o, s);
+    rtk::query_form(t, inst, [&](auto f) {
+        typedef decltype(f) F;
+        hipLaunchKernelGGL((rtk::sample_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(rtk::sample_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, t, o);
+    });
     return hipGetLastError();
 }
 

@@ -76,29 +76,16 @@ __global__ __launch_bounds__(kQueryThreads) void shade_spheres(const RtFrameArgs
     shade_finish(A, sc, rays, flags, out, i, e);
 }
 
-template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-static void launch_st(const RtFrameArgs& a, const RtTriScene& t, const float4* rays, uint32_t flags, float4* out, uint32_t n, hipStream_t s) {
-    const uint32_t blocks = (uint32_t)(((size_t)n + kQueryThreads - 1u) / kQueryThreads);
-    hipLaunchKernelGGL((shade_triangles<STK, PACKED, PAIRS, P16, INST>), dim3(blocks), dim3(kQueryThreads), 0, s, a, t, rays, flags, out, n);
-}
-template <bool INST>
-static void launch_st_walk(const RtFrameArgs& a, const RtTriScene& t, const float4* rays, uint32_t flags, float4* out, uint32_t n, hipStream_t s) {
-    if (t.n_nodes <= 65536u && t.packed_ok) launch_st<uint16_t, true, false, false, INST>(a, t, rays, flags, out, n, s);
-    else if (t.n_nodes <= 65536u)          launch_st<uint16_t, false, false, false, INST>(a, t, rays, flags, out, n, s);
-    else                                   launch_st<uint32_t, false, false, false, INST>(a, t, rays, flags, out, n, s);
-}
-
 }  // namespace rtk
 
-// the forms of rt_launch_limited_triangles (rt_query.hip: launch_lt_form)
 hipError_t rt_launch_shade_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const float4* rays, uint32_t flags, float4* out,
                                      uint32_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    const bool pairs = inst && t.pairs && t.n_nodes <= 65536u && t.packed_ok && t.n_blas <= rtk::kWideBlas;
-    if (pairs && t.p16_ok) rtk::launch_st<uint16_t, true, true, true, true>(a, t, rays, flags, out, n, s);
-    else if (pairs)        rtk::launch_st<uint16_t, true, true, false, true>(a, t, rays, flags, out, n, s);
-    else if (inst)         rtk::launch_st_walk<true>(a, t, rays, flags, out, n, s);
-    else                   rtk::launch_st_walk<false>(a, t, rays, flags, out, n, s);
+    const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
+    rtk::query_form(t, inst, [&](auto f) {
+        typedef decltype(f) F;
+        hipLaunchKernelGGL((rtk::shade_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(blocks), dim3(rtk::kQueryThreads), 0, s, a, t, rays, flags, out, n);
+    });
     return hipGetLastError();
 }
 

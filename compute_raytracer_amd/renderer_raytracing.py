@@ -8,6 +8,7 @@ itself (RR:102-109); the blit to the canvas (RR:449-463) has no counterpart.
 
 No CPU fallback: without librt355.so and a gfx950 device, `initialize()` raises.
 """
+import contextlib
 import ctypes
 
 import numpy as np
@@ -306,15 +307,59 @@ class RendererRaytracing:
             rays[:, word] = lim
         return rays
 
-    def _trace_rays_torch(self, rays, directions, out, flags, occlusion):
+    @contextlib.contextmanager
+    def _current_stream(self, device):
+        """The stream handle with which a query runs on torch.cuda.current_stream(device).  torch's default stream has the handle
+        0, which the C ABI reads as "the context's stream": the query then goes through a stream of our own, ordered after and
+        before the default stream."""
         import torch
-        name = "occluded" if occlusion else "trace_rays"
+        cur = torch.cuda.current_stream(device)
+        run = cur
+        if cur.cuda_stream == 0:
+            if getattr(self, "_query_stream", None) is None:
+                self._query_stream = torch.cuda.Stream(device)
+            run = self._query_stream
+            run.wait_stream(cur)
+        yield ctypes.c_void_p(run.cuda_stream)
+        if run is not cur:
+            cur.wait_stream(run)
+
+    def _check_ray_tensor(self, name, rays, directions):
+        import torch
         if directions is not None:
             raise ValueError("%s: a tensor argument is the (n, 8) ray buffer itself" % name)
         if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
             raise ValueError("%s: rays must be a contiguous float32 (n, 8) tensor" % name)
         if rays.device.type != "cuda" or rays.device.index != self.device:
             raise ValueError("%s: rays must live on cuda:%d, this renderer's device" % (name, self.device))
+
+    def _parse_rect(self, name, rect):
+        """rect = (x0, y0, w, h) or None, the whole frame -> (what the C ABI takes, w, h)"""
+        if rect is None:
+            return None, self.width, self.height
+        x0, y0, w, h = (int(v) for v in rect)
+        if min(x0, y0, w, h) < 0 or max(x0, y0, w, h) > 0xFFFFFFFF:
+            raise ValueError("%s: rect is (x0, y0, w, h), four unsigned 32-bit numbers" % name)
+        return (ctypes.c_uint32 * 4)(x0, y0, w, h), w, h
+
+    def _check_plane_tensors(self, name, table, w, h, out):
+        """out: a dict of (h, w) + tail tensors named and typed as `table` (abi.GBUFFER_PLANES, abi.AO_PLANES) says -> their device"""
+        import torch
+        if not isinstance(out, dict) or not out or any(n not in table for n in out):
+            raise ValueError("%s: out is a dict of tensors named %s" % (name, ", ".join(table)))
+        for n, t in out.items():
+            tail, dtype, _ = table[n]
+            want = {"<i4": torch.int32, "u1": torch.uint8, "<f4": torch.float32}[dtype]
+            if type(t).__module__.split(".")[0] != "torch" or t.dtype != want or tuple(t.shape) != (h, w) + tail or not t.is_contiguous():
+                raise ValueError("%s: out[%r] must be a contiguous %s tensor of shape %r" % (name, n, want, (h, w) + tail))
+            if t.device.type != "cuda" or t.device.index != self.device:
+                raise ValueError("%s: out must live on cuda:%d, this renderer's device" % (name, self.device))
+        return next(iter(out.values())).device
+
+    def _trace_rays_torch(self, rays, directions, out, flags, occlusion):
+        import torch
+        name = "occluded" if occlusion else "trace_rays"
+        self._check_ray_tensor(name, rays, directions)
         if occlusion:
             if out is None:
                 out = torch.empty((rays.shape[0],), dtype=torch.uint8, device=rays.device)
@@ -325,25 +370,15 @@ class RendererRaytracing:
         elif out.element_size() != 4 or tuple(out.shape) != (rays.shape[0], 8) or not out.is_contiguous() or out.device != rays.device:
             raise ValueError("trace_rays: out must be a contiguous 32-bit (n, 8) tensor on the rays' device")
         self.recalculateScene()
-        cur = torch.cuda.current_stream(rays.device)
-        # (torch's default stream has the handle 0, which the C ABI reads as "the context's stream": go through a stream of our own
-        # ordered after and before it)
-        run = cur
-        if cur.cuda_stream == 0:
-            if getattr(self, "_query_stream", None) is None:
-                self._query_stream = torch.cuda.Stream(rays.device)
-            run = self._query_stream
-            run.wait_stream(cur)
         args = (self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0])
-        tail = (ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(run.cuda_stream))
-        if occlusion:
-            abi.check(self._lib.rt_occluded(*args, flags, *tail), self._ctx)
-        elif flags:
-            abi.check(self._lib.rt_trace_rays_ex(*args, flags, *tail), self._ctx)
-        else:
-            abi.check(self._lib.rt_trace_rays(*args, *tail), self._ctx)
-        if run is not cur:
-            cur.wait_stream(run)
+        with self._current_stream(rays.device) as stream:
+            tail = (ctypes.c_void_p(out.data_ptr()), stream)
+            if occlusion:
+                abi.check(self._lib.rt_occluded(*args, flags, *tail), self._ctx)
+            elif flags:
+                abi.check(self._lib.rt_trace_rays_ex(*args, flags, *tail), self._ctx)
+            else:
+                abi.check(self._lib.rt_trace_rays(*args, *tail), self._ctx)
         return out
 
     # ---- multi-hit queries: the k nearest hits of the host's rays (rt_trace_rays_multi / rt_trace_rays_multi_host) -------------
@@ -375,28 +410,15 @@ class RendererRaytracing:
 
     def _trace_rays_multi_torch(self, rays, directions, k, flags, out):
         import torch
-        if directions is not None:
-            raise ValueError("trace_rays_multi: a tensor argument is the (n, 8) ray buffer itself")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("trace_rays_multi: rays must be a contiguous float32 (n, 8) tensor")
-        if rays.device.type != "cuda" or rays.device.index != self.device:
-            raise ValueError("trace_rays_multi: rays must live on cuda:%d, this renderer's device" % self.device)
+        self._check_ray_tensor("trace_rays_multi", rays, directions)
         if out is None:
             out = torch.empty((rays.shape[0], max(k, 0), 8), dtype=torch.float32, device=rays.device)
         elif out.element_size() != 4 or tuple(out.shape) != (rays.shape[0], k, 8) or not out.is_contiguous() or out.device != rays.device:
             raise ValueError("trace_rays_multi: out must be a contiguous 32-bit (n, k, 8) tensor on the rays' device")
         self.recalculateScene()
-        cur = torch.cuda.current_stream(rays.device)
-        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
-        if cur.cuda_stream == 0:
-            if getattr(self, "_query_stream", None) is None:
-                self._query_stream = torch.cuda.Stream(rays.device)
-            run = self._query_stream
-            run.wait_stream(cur)
-        abi.check(self._lib.rt_trace_rays_multi(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0], flags, k,
-                                                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(run.cuda_stream)), self._ctx)
-        if run is not cur:
-            cur.wait_stream(run)
+        with self._current_stream(rays.device) as stream:
+            abi.check(self._lib.rt_trace_rays_multi(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0], flags, k,
+                                                    ctypes.c_void_p(out.data_ptr()), stream), self._ctx)
         return out
 
     # ---- shaded ray queries: the renderer's colour along the host's rays (rt_shade_rays / rt_shade_rays_host) -----------------
@@ -423,28 +445,15 @@ class RendererRaytracing:
 
     def _shade_rays_torch(self, rays, directions, out, flags):
         import torch
-        if directions is not None:
-            raise ValueError("shade_rays: a tensor argument is the (n, 8) ray buffer itself")
-        if rays.dtype != torch.float32 or rays.dim() != 2 or rays.shape[1] != 8 or not rays.is_contiguous():
-            raise ValueError("shade_rays: rays must be a contiguous float32 (n, 8) tensor")
-        if rays.device.type != "cuda" or rays.device.index != self.device:
-            raise ValueError("shade_rays: rays must live on cuda:%d, this renderer's device" % self.device)
+        self._check_ray_tensor("shade_rays", rays, directions)
         if out is None:
             out = torch.empty((rays.shape[0], 4), dtype=torch.float32, device=rays.device)
         elif out.dtype != torch.float32 or tuple(out.shape) != (rays.shape[0], 4) or not out.is_contiguous() or out.device != rays.device:
             raise ValueError("shade_rays: out must be a contiguous float32 (n, 4) tensor on the rays' device")
         self.recalculateScene()
-        cur = torch.cuda.current_stream(rays.device)
-        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
-        if cur.cuda_stream == 0:
-            if getattr(self, "_query_stream", None) is None:
-                self._query_stream = torch.cuda.Stream(rays.device)
-            run = self._query_stream
-            run.wait_stream(cur)
-        abi.check(self._lib.rt_shade_rays(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0], flags,
-                                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(run.cuda_stream)), self._ctx)
-        if run is not cur:
-            cur.wait_stream(run)
+        with self._current_stream(rays.device) as stream:
+            abi.check(self._lib.rt_shade_rays(self._ctx, ctypes.c_void_p(rays.data_ptr()), rays.shape[0], flags,
+                                              ctypes.c_void_p(out.data_ptr()), stream), self._ctx)
         return out
 
     # ---- supersampled frames: s x s camera rays per pixel, resolved on the device (rt_render_samples / rt_render_samples_host) ----
@@ -485,20 +494,11 @@ class RendererRaytracing:
         if img is None and flt is None:
             raise ValueError("render_samples: out holds no tensor")
         self.recalculateScene()
-        dev = (img if img is not None else flt).device
-        cur = torch.cuda.current_stream(dev)
-        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
-        if cur.cuda_stream == 0:
-            if getattr(self, "_query_stream", None) is None:
-                self._query_stream = torch.cuda.Stream(dev)
-            run = self._query_stream
-            run.wait_stream(cur)
-        abi.check(self._lib.rt_render_samples(self._ctx, s, ctypes.c_void_p(img.data_ptr()) if img is not None else None,
-                                              img.numel() if img is not None else 0,
-                                              ctypes.c_void_p(flt.data_ptr()) if flt is not None else None,
-                                              4 * flt.numel() if flt is not None else 0, ctypes.c_void_p(run.cuda_stream)), self._ctx)
-        if run is not cur:
-            cur.wait_stream(run)
+        with self._current_stream((img if img is not None else flt).device) as stream:
+            abi.check(self._lib.rt_render_samples(self._ctx, s, ctypes.c_void_p(img.data_ptr()) if img is not None else None,
+                                                  img.numel() if img is not None else 0,
+                                                  ctypes.c_void_p(flt.data_ptr()) if flt is not None else None,
+                                                  4 * flt.numel() if flt is not None else 0, stream), self._ctx)
         return out
 
     # ---- geometry frames: depth, normal, ids and uv of what the camera sees, as planes (rt_render_gbuffer / rt_render_gbuffer_host) ----
@@ -511,14 +511,7 @@ class RendererRaytracing:
         numpy (out=None): a dict of the arrays named in `planes`, through rt_render_gbuffer_host.  torch: `out` is a dict of
         contiguous tensors of those shapes and dtypes on this renderer's device, any non-empty subset of the four names (`planes` is
         then not read) -> `out`, enqueued through rt_render_gbuffer on torch.cuda.current_stream()."""
-        if rect is None:
-            x0, y0, w, h = 0, 0, self.width, self.height
-            c_rect = None
-        else:
-            x0, y0, w, h = (int(v) for v in rect)
-            if min(x0, y0, w, h) < 0 or max(x0, y0, w, h) > 0xFFFFFFFF:
-                raise ValueError("render_gbuffer: rect is (x0, y0, w, h), four unsigned 32-bit numbers")
-            c_rect = (ctypes.c_uint32 * 4)(x0, y0, w, h)
+        c_rect, w, h = self._parse_rect("render_gbuffer", rect)
         if out is not None:
             return self._render_gbuffer_torch(c_rect, w, h, out)
         names = [planes] if isinstance(planes, str) else list(planes)
@@ -531,29 +524,11 @@ class RendererRaytracing:
         return res
 
     def _render_gbuffer_torch(self, c_rect, w, h, out):
-        import torch
-        if not isinstance(out, dict) or not out or any(n not in abi.GBUFFER_PLANES for n in out):
-            raise ValueError("render_gbuffer: out is a dict of tensors named %s" % ", ".join(abi.GBUFFER_PLANES))
-        for n, t in out.items():
-            tail, dtype, _ = abi.GBUFFER_PLANES[n]
-            want = torch.int32 if dtype == "<i4" else torch.float32
-            if type(t).__module__.split(".")[0] != "torch" or t.dtype != want or tuple(t.shape) != (h, w) + tail or not t.is_contiguous():
-                raise ValueError("render_gbuffer: out[%r] must be a contiguous %s tensor of shape %r" % (n, want, (h, w) + tail))
-            if t.device.type != "cuda" or t.device.index != self.device:
-                raise ValueError("render_gbuffer: out must live on cuda:%d, this renderer's device" % self.device)
+        dev = self._check_plane_tensors("render_gbuffer", abi.GBUFFER_PLANES, w, h, out)
         self.recalculateScene()
-        dev = next(iter(out.values())).device
-        cur = torch.cuda.current_stream(dev)
-        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
-        if cur.cuda_stream == 0:
-            if getattr(self, "_query_stream", None) is None:
-                self._query_stream = torch.cuda.Stream(dev)
-            run = self._query_stream
-            run.wait_stream(cur)
         gb = abi.RtGbuffer(**{n: t.data_ptr() for n, t in out.items()})
-        abi.check(self._lib.rt_render_gbuffer(self._ctx, c_rect, ctypes.byref(gb), w * h, ctypes.c_void_p(run.cuda_stream)), self._ctx)
-        if run is not cur:
-            cur.wait_stream(run)
+        with self._current_stream(dev) as stream:
+            abi.check(self._lib.rt_render_gbuffer(self._ctx, c_rect, ctypes.byref(gb), w * h, stream), self._ctx)
         return out
 
     # ---- ambient-occlusion frames: k occlusion rays per pixel over the hemisphere of what the camera sees (rt_render_ao / rt_render_ao_host) ----
@@ -570,14 +545,7 @@ class RendererRaytracing:
         dirs = ao_directions(k) if directions is None else np.ascontiguousarray(directions, dtype=np.float32)
         if dirs.ndim != 2 or dirs.shape[1] != 3 or not 1 <= dirs.shape[0] <= abi.RT355_MAX_AO_RAYS:
             raise ValueError("render_ao: directions is (k, 3) with 1 <= k <= %d" % abi.RT355_MAX_AO_RAYS)
-        if rect is None:
-            x0, y0, w, h = 0, 0, self.width, self.height
-            c_rect = None
-        else:
-            x0, y0, w, h = (int(v) for v in rect)
-            if min(x0, y0, w, h) < 0 or max(x0, y0, w, h) > 0xFFFFFFFF:
-                raise ValueError("render_ao: rect is (x0, y0, w, h), four unsigned 32-bit numbers")
-            c_rect = (ctypes.c_uint32 * 4)(x0, y0, w, h)
+        c_rect, w, h = self._parse_rect("render_ao", rect)
         args = (self._ctx, c_rect, dirs.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), dirs.shape[0], float(tmin), float(radius))
         if out is not None:
             return self._render_ao_torch(args, w, h, out)
@@ -591,28 +559,11 @@ class RendererRaytracing:
         return res
 
     def _render_ao_torch(self, args, w, h, out):
-        import torch
-        if not isinstance(out, dict) or not out or any(n not in abi.AO_PLANES for n in out):
-            raise ValueError("render_ao: out is a dict of tensors named %s" % ", ".join(abi.AO_PLANES))
-        for n, t in out.items():
-            want = torch.uint8 if n == "count" else torch.float32
-            if type(t).__module__.split(".")[0] != "torch" or t.dtype != want or tuple(t.shape) != (h, w) or not t.is_contiguous():
-                raise ValueError("render_ao: out[%r] must be a contiguous %s tensor of shape %r" % (n, want, (h, w)))
-            if t.device.type != "cuda" or t.device.index != self.device:
-                raise ValueError("render_ao: out must live on cuda:%d, this renderer's device" % self.device)
+        dev = self._check_plane_tensors("render_ao", abi.AO_PLANES, w, h, out)
         self.recalculateScene()
-        dev = next(iter(out.values())).device
-        cur = torch.cuda.current_stream(dev)
-        run = cur                                    # (the default stream's handle is 0: see _trace_rays_torch)
-        if cur.cuda_stream == 0:
-            if getattr(self, "_query_stream", None) is None:
-                self._query_stream = torch.cuda.Stream(dev)
-            run = self._query_stream
-            run.wait_stream(cur)
         ao = abi.RtAo(**{n: t.data_ptr() for n, t in out.items()})
-        abi.check(self._lib.rt_render_ao(*args, ctypes.byref(ao), w * h, ctypes.c_void_p(run.cuda_stream)), self._ctx)
-        if run is not cur:
-            cur.wait_stream(run)
+        with self._current_stream(dev) as stream:
+            abi.check(self._lib.rt_render_ao(*args, ctypes.byref(ao), w * h, stream), self._ctx)
         return out
 
     def pick(self, x, y):

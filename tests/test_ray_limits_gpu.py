@@ -368,6 +368,20 @@ def test_device_and_host_paths_agree_and_no_scene_is_refused():
             assert fn(r._ctx, rays.ctypes.data, 4, 6, occ.ctypes.data) == abi.RT_ERR_INVALID_ARG
         assert lib.rt_trace_rays_ex(r._ctx, dev_rays.data_ptr() + 4, 1, 0, hits.data_ptr(), None) == abi.RT_ERR_INVALID_ARG
         assert lib.rt_occluded(r._ctx, dev_rays.data_ptr(), 1, 0, out.data_ptr() + 1, None) == abi.RT_OK   # no alignment needed
+        # the messages whole -- each names its entry point and what it asks to be aligned -- and the order when two arguments are wrong
+        err = lambda: lib.rt_last_error(r._ctx)
+        for fn, name, nouns in ((lib.rt_trace_rays_ex, b"rt_trace_rays_ex", b"rays and hits"), (lib.rt_occluded, b"rt_occluded", b"rays")):
+            assert fn(r._ctx, dev_rays.data_ptr() + 4, 1, L, hits.data_ptr(), None) == abi.RT_ERR_INVALID_ARG
+            assert err() == name + b": " + nouns + b" must be 16-byte aligned"
+            assert fn(r._ctx, None, 4, L, hits.data_ptr(), None) == abi.RT_ERR_INVALID_ARG and err() == name + b": NULL argument"
+            assert fn(r._ctx, None, 4, 2, None, None) == abi.RT_ERR_INVALID_ARG and err() == name + b": unknown flag bits 0x2"   # flags first
+            assert fn(r._ctx, None, 4, L, hits.data_ptr() + 4, None) == abi.RT_ERR_INVALID_ARG and err() == name + b": NULL argument"
+        assert lib.rt_trace_rays_ex(r._ctx, dev_rays.data_ptr(), 1, 0, hits.data_ptr() + 4, None) == abi.RT_ERR_INVALID_ARG
+        assert err() == b"rt_trace_rays_ex: rays and hits must be 16-byte aligned"
+        for fn, name in ((lib.rt_trace_rays_host_ex, b"rt_trace_rays_host_ex"), (lib.rt_occluded_host, b"rt_occluded_host")):
+            assert fn(r._ctx, None, 4, 0, occ.ctypes.data) == abi.RT_ERR_INVALID_ARG and err() == name + b": NULL argument"
+            assert fn(r._ctx, None, 4, 6, None) == abi.RT_ERR_INVALID_ARG and err() == name + b": unknown flag bits 0x6"
+        assert lib.rt_occluded_host(r._ctx, rays.ctypes.data + 4, 1, L, np.zeros(1, np.uint8).ctypes.data) == abi.RT_OK   # host memory: any address
         torch.cuda.synchronize()
     finally:
         r.close()
@@ -379,6 +393,7 @@ def test_device_and_host_paths_agree_and_no_scene_is_refused():
         for flags in (0, L):
             assert bare._lib.rt_trace_rays_host_ex(bare._ctx, rays.ctypes.data, 1, flags, hits.ctypes.data) == abi.RT_ERR_STATE
             assert bare._lib.rt_occluded_host(bare._ctx, rays.ctypes.data, 1, flags, occ.ctypes.data) == abi.RT_ERR_STATE
+            assert bare._lib.rt_last_error(bare._ctx) == b"rt_occluded_host: no scene has been written"
         assert bare._lib.rt_occluded_host(bare._ctx, rays.ctypes.data, 1, 2, occ.ctypes.data) == abi.RT_ERR_INVALID_ARG
     finally:
         bare.close()

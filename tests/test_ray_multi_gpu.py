@@ -313,6 +313,16 @@ def test_device_and_host_paths_agree_and_no_scene_is_refused():
         assert lib.rt_trace_rays_multi_host(r._ctx, rays.ctypes.data, 4, 0, 4, None) == abi.RT_ERR_INVALID_ARG
         assert lib.rt_trace_rays_multi(r._ctx, dev_rays.data_ptr() + 4, 1, 0, 4, hits.data_ptr(), None) == abi.RT_ERR_INVALID_ARG
         assert lib.rt_trace_rays_multi(r._ctx, dev_rays.data_ptr(), 4, 0, 9, hits.data_ptr(), None) == abi.RT_ERR_INVALID_ARG
+        # the messages whole, and the order when two arguments are wrong: flags, k, pointers, alignment
+        err = lambda: lib.rt_last_error(r._ctx)
+        k_msg = b": k = 9 is outside 1 .. RT355_MAX_HITS (%d)" % abi.RT355_MAX_HITS
+        for fn, name, tail in ((lib.rt_trace_rays_multi, b"rt_trace_rays_multi", (None,)), (lib.rt_trace_rays_multi_host, b"rt_trace_rays_multi_host", ())):
+            assert fn(r._ctx, None, 4, 2, 9, None, *tail) == abi.RT_ERR_INVALID_ARG and err() == name + b": unknown flag bits 0x2"
+            assert fn(r._ctx, None, 4, L, 9, None, *tail) == abi.RT_ERR_INVALID_ARG and err() == name + k_msg
+            assert fn(r._ctx, None, 4, L, 4, None, *tail) == abi.RT_ERR_INVALID_ARG and err() == name + b": NULL argument"
+        for off_rays, off_hits in ((4, 0), (0, 4)):
+            assert lib.rt_trace_rays_multi(r._ctx, dev_rays.data_ptr() + off_rays, 1, 0, 4, hits.data_ptr() + off_hits, None) == abi.RT_ERR_INVALID_ARG
+            assert err() == b"rt_trace_rays_multi: rays and hits must be 16-byte aligned"
         torch.cuda.synchronize()
     finally:
         r.close()
@@ -322,6 +332,7 @@ def test_device_and_host_paths_agree_and_no_scene_is_refused():
         hits = np.zeros((1, 4), dtype=abi.HIT_DTYPE)
         for flags in (0, L):
             assert bare._lib.rt_trace_rays_multi_host(bare._ctx, rays.ctypes.data, 1, flags, 4, hits.ctypes.data) == abi.RT_ERR_STATE
+            assert bare._lib.rt_last_error(bare._ctx) == b"rt_trace_rays_multi_host: no scene has been written"
     finally:
         bare.close()
 

@@ -245,6 +245,17 @@ def test_device_host_and_pick_paths_agree():
         assert lib.rt_trace_rays(r._ctx, None, 0, None, None) == abi.RT_OK
         assert lib.rt_pick(r._ctx, None, 0, None) == abi.RT_OK
         assert lib.rt_trace_rays_host(r._ctx, None, 4, None) == abi.RT_ERR_INVALID_ARG
+        # the messages whole: NULL pointers, misalignment (the pointers are looked at first), a pixel outside the frame
+        err = lambda: lib.rt_last_error(r._ctx)
+        assert err() == b"rt_trace_rays_host: NULL argument"
+        dev_rays = torch.from_numpy(rays).to("cuda:0")
+        assert lib.rt_trace_rays(r._ctx, None, 4, out.data_ptr() + 4, None) == abi.RT_ERR_INVALID_ARG and err() == b"rt_trace_rays: NULL argument"
+        for off_rays, off_hits in ((4, 0), (0, 4)):
+            assert lib.rt_trace_rays(r._ctx, dev_rays.data_ptr() + off_rays, 1, out.data_ptr() + off_hits, None) == abi.RT_ERR_INVALID_ARG
+            assert err() == b"rt_trace_rays: rays and hits must be 16-byte aligned"
+        assert lib.rt_pick(r._ctx, None, 4, hits.ctypes.data) == abi.RT_ERR_INVALID_ARG and err() == b"rt_pick: NULL argument"
+        outside = np.array([[0, 0], [W, 0]], np.uint32)
+        assert lib.rt_pick(r._ctx, outside.ctypes.data, 2, hits.ctypes.data) == abi.RT_ERR_INVALID_ARG and err() == b"rt_pick: pixel outside the frame"
     finally:
         r.close()
     # a context without a scene
@@ -254,6 +265,7 @@ def test_device_host_and_pick_paths_agree():
         rays[0, 6] = -1.0
         hits = np.zeros(1, dtype=abi.HIT_DTYPE)
         assert bare._lib.rt_trace_rays_host(bare._ctx, rays.ctypes.data, 1, hits.ctypes.data) == abi.RT_ERR_STATE
+        assert bare._lib.rt_last_error(bare._ctx) == b"rt_trace_rays_host: no scene has been written"
         xy = np.zeros((1, 2), np.uint32)
         assert bare._lib.rt_pick(bare._ctx, xy.ctypes.data, 1, hits.ctypes.data) == abi.RT_ERR_STATE
     finally:

@@ -171,7 +171,7 @@ TRI = tri_cases()
 @pytest.mark.parametrize("name,flat", [(k, False) for k in TRI] + [("inst3", True)])
 def test_compose_equals_the_frame_triangles(oracle, constant_sky, name, flat):
     """The cases of tests/test_ray_query_gpu.py that between them reach every launch form (rt_shade.hip: the selection of
-    launch_lt_form).  Before the first frame the context has no relinked pair records: staged instances with the node walk, and
+    rt_query_form.h).  Before the first frame the context has no relinked pair records: staged instances with the node walk, and
     the per-frame buffer versions for seventeen instances; a frame builds the records where the scene fits them, and the same
     rays then go through the pair forms, with 16-bit entries where every meta fits them."""
     scene, mat = TRI[name]()
@@ -360,6 +360,14 @@ def test_device_out_and_host_paths_agree_and_arguments_are_checked():
         assert lib.rt_shade_rays_host(r._ctx, None, 4, 0, raw.ctypes.data) == abi.RT_ERR_INVALID_ARG
         assert lib.rt_shade_rays_host(r._ctx, rays.ctypes.data, 4, 0, None) == abi.RT_ERR_INVALID_ARG
         assert lib.rt_shade_rays_host(r._ctx, None, 0, 0, None) == abi.RT_OK
+        # the messages whole, and the order when two arguments are wrong: flags, pointers, alignment
+        err = lambda: lib.rt_last_error(r._ctx)
+        for off_rays, off_out in ((4, 0), (0, 8)):
+            assert lib.rt_shade_rays(r._ctx, vp(dev.data_ptr() + off_rays), 8, 0, vp(out.data_ptr() + off_out), None) == abi.RT_ERR_INVALID_ARG
+            assert err() == b"rt_shade_rays: rays and out must be 16-byte aligned"
+        for fn, name, tail in ((lib.rt_shade_rays, b"rt_shade_rays", (None,)), (lib.rt_shade_rays_host, b"rt_shade_rays_host", ())):
+            assert fn(r._ctx, None, 4, 2, None, *tail) == abi.RT_ERR_INVALID_ARG and err() == name + b": unknown flag bits 0x2"
+            assert fn(r._ctx, None, 4, 0, vp(out.data_ptr() + 8), *tail) == abi.RT_ERR_INVALID_ARG and err() == name + b": NULL argument"
         assert lib.rt_shade_rays(r._ctx, None, 0, abi.RT_SHADE_COMPOSE, None, None) == abi.RT_OK
     finally:
         r.close()
