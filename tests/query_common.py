@@ -15,8 +15,18 @@ def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
-def same(a, b):
-    return np.array_equal(bits(a), bits(b))
+def differ(a, b):
+    """Elementwise: the float32 words differ as bits (the sign of zero and a NaN's payload included).  The comparisons below take
+    another rule of the same shape through their `differ` argument (tests/tri_edge_common.py has one)."""
+    return bits(a) != bits(b)
+
+
+def same(a, b, differ=differ):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and not differ(a, b).any()
+
+
+_same = same                                            # (the comparisons below rebind `same` to their own rule)
 
 
 # ---- rays --------------------------------------------------------------------------------------------------------------------
@@ -110,11 +120,12 @@ def restate_triangle_hits(buf, o, d, prim, inst):
     return t, u, v, nrm
 
 
-def check_triangle_hits(oracle, buf, o, d, h):
+def check_triangle_hits(oracle, buf, o, d, h, differ=differ):
+    same = lambda a, b: _same(a, b, differ)
     t_ref = oracle.trace_tri_rays(buf, o, d)
     miss = h["prim"] < 0
     assert np.array_equal(miss, t_ref == F(-1.0)), "miss sets differ: %d vs %d" % (miss.sum(), (t_ref == -1).sum())
-    assert same(h["t"], t_ref), "t differs from the oracle on %d rays" % int((bits(h["t"]) != bits(t_ref)).sum())
+    assert same(h["t"], t_ref), "t differs from the oracle on %d rays" % int(differ(h["t"], t_ref).sum())
     assert np.all(h["instance"][miss] == -1) and np.all(h["u"][miss] == 0) and np.all(h["v"][miss] == 0)
     assert np.all(h["normal"][miss] == 0)
     hit = ~miss
@@ -125,6 +136,107 @@ def check_triangle_hits(oracle, buf, o, d, h):
         assert same(t, h["t"][hit]) and same(u, h["u"][hit]) and same(v, h["v"][hit])
         assert same(nrm, h["normal"][hit])
     return int(hit.sum())
+
+
+# ---- the box test and the triangle test, term by term (tests/tri_edge_common.py counts their edge cases) ---------------------------
+def u32f(f):
+    """WGSL u32(f32): truncating, saturating, NaN and negatives -> 0"""
+    f = float(f)
+    if not f > 0.0:
+        return 0
+    return 4294967295 if f >= 4294967040.0 else int(f)
+
+
+def hit_aabb(lo, hi, o, inv, terms=False):
+    """hitAABB (RK:395-410) in float32 for boxes lo / hi (3,) or (n, 3) and rays o, inv = 1 / d (n, 3): the entry distance, 99999
+    on a miss.  fmin / fmax drop a NaN operand as C's fminf / fmaxf do.  terms: also the six slab products t1, t2."""
+    t1 = (np.asarray(lo, F) - o) * inv                               # RK:397
+    t2 = (np.asarray(hi, F) - o) * inv                               # RK:398
+    lo3, hi3 = np.fmin(t1, t2), np.fmax(t1, t2)                      # RK:399-400
+    t_min = np.fmax(np.fmax(lo3[..., 0], lo3[..., 1]), lo3[..., 2])  # RK:402
+    t_max = np.fmin(np.fmin(hi3[..., 0], hi3[..., 1]), hi3[..., 2])  # RK:403
+    dist = np.where((t_min > t_max) | (t_max < F(0.0)), F(99999.0), t_min).astype(F)   # RK:405-409
+    return (dist, t1, t2) if terms else dist
+
+
+def walk_leaves(nodes, root, o, d, limit, visit=None):
+    """The leaves of the tree under node `root` a walk (RK:179-240, RK:271-330) can reach for rays o, d (n, 3): [(left, count,
+    mask (n,))], mask = no box on the way down was missed or entered beyond `limit` (the value the running nearest hit starts
+    from: it only falls).  The root's own box is not tested, as in the reference.  visit(child index, dist, t1, t2, mask) sees
+    every box test.  Indices clamp to the last node; a buffer that is no tree is cut off after 4 n node visits."""
+    nodes = np.asarray(nodes, F).reshape(-1, 8)
+    last = nodes.shape[0] - 1
+    inv = F(1.0) / d
+    out, todo, budget = [], [(min(int(root), last), np.ones(o.shape[0], bool))], 4 * nodes.shape[0] + 4
+    while todo and budget > 0:
+        budget -= 1
+        i, mask = todo.pop()
+        left, count = u32f(nodes[i, 3]), u32f(nodes[i, 7])
+        if count:
+            out.append((left, count, mask))
+            continue
+        for c in (left, (left + 1) & 0xFFFFFFFF):
+            c = min(c, last)
+            dist, t1, t2 = hit_aabb(nodes[c, 0:3], nodes[c, 4:7], o, inv, terms=True)
+            if visit is not None:
+                visit(c, dist, t1, t2, mask)
+            m = mask & ~(dist > limit)
+            if m.any():
+                todo.append((c, m))
+    return out
+
+
+def reach(buf, o, d, limit, visit=None):
+    """{instance record: (slots, mask (n, len(slots)))}: the lookup slots whose leaf the two-level walk can reach per ray, by
+    walk_leaves over the top-level tree and then over each instance's tree in its object space.  visit(instance record or None
+    for the top level, direction there (n, 3), dist, t1, t2, mask) sees every box test a ray can come to."""
+    nodes = np.asarray(buf["nodes"], F).reshape(-1, 8)
+    blas = np.asarray(buf["blas"], F).reshape(-1, 20)
+    look = np.asarray(buf["blas_lookup"], F)
+    n, n_slots = o.shape[0], len(buf["tri_lookup"])
+    limit = np.broadcast_to(np.asarray(limit, F), (n,))
+    per_inst = {}
+    top = None if visit is None else (lambda c, dist, t1, t2, m: visit(None, d, dist, t1, t2, m))
+    for left, count, mask in walk_leaves(nodes, 0, o, d, limit, top):
+        for k in range(min(count, len(look))):
+            bi = min(u32f(look[min(left + k, len(look) - 1)]), blas.shape[0] - 1)
+            per_inst[bi] = per_inst.get(bi, np.zeros(n, bool)) | mask
+    out = {}
+    for bi, mask in per_inst.items():
+        m = np.broadcast_to(blas[bi], (n, 20))
+        oo, od = mat_apply(m, o, 1.0), mat_apply(m, d, 0.0)
+        got = {}
+        low = None if visit is None else (lambda c, dist, t1, t2, lm, bi=bi, od=od, mask=mask: visit(bi, od, dist, t1, t2, lm & mask))
+        for left, count, lm in walk_leaves(nodes, u32f(blas[bi, 16]), oo, od, limit, low):
+            for k in range(min(count, 4 * n_slots)):
+                s = min(left + k, n_slots - 1)
+                got[s] = got.get(s, np.zeros(n, bool)) | (lm & mask)
+        slots = np.array(sorted(got), np.int64)
+        out[bi] = (slots, np.stack([got[s] for s in slots], axis=1) if slots.size else np.zeros((n, 0), bool))
+    return out
+
+
+def triangle_terms(m, tris, o, d):
+    """hitTriangle's terms (RK:354-379) for n rays against P triangles (P, 40) in the object space of instance record m (20,), each
+    (n, P) float32 in the oracle's order: det, u, v (before the division), tnum = dot(edge2, sCrossEdge1), t, and `ok`, the
+    tests of RK:359-372 passed -- written as the shader's rejections, so a NaN passes where it passes there."""
+    n = o.shape[0]
+    mm = np.broadcast_to(np.asarray(m, F), (n, 20))
+    oo, od = mat_apply(mm, o, 1.0), mat_apply(mm, d, 0.0)
+    A, B, C = tris[:, 0:3], tris[:, 12:15], tris[:, 24:27]
+    e1, e2 = (B - A)[None], (C - A)[None]
+    shape = (n,) + e2.shape[1:]
+    odc = np.broadcast_to(od[:, None, :], shape)
+    rce2 = cross(odc, np.broadcast_to(e2, shape))
+    det = dot(e1, rce2)
+    s = oo[:, None, :] - A[None]
+    u = dot(s, rce2)
+    sce1 = cross(s, np.broadcast_to(e1, shape))
+    v = dot(odc, sce1)
+    tnum = dot(np.broadcast_to(e2, shape), sce1)
+    t = (F(1.0) / det) * tnum
+    ok = ~(det < F(0.00001)) & ~((u < 0) | (u > det)) & ~((v < 0) | (u + v > det))
+    return dict(det=det, u=u, v=v, tnum=tnum, t=t, ok=ok, oo=oo, od=od)
 
 
 # ---- triangles: the float32 brute force ---------------------------------------------------------------------------------------
@@ -143,9 +255,25 @@ def blas_slots(buf, root):
     return np.unique(np.asarray(out, np.int64))
 
 
-def brute_triangles(buf, o, d, tmin, tmax):
+def brute_triangles(buf, o, d, tmin, tmax, boxes=False):
     """The smallest t that hit_triangle (RK:344-381) accepts within (tmin, tmax) over every (triangle, instance) pair, in the
-    same float32 operations; +inf where none does."""
+    same float32 operations; +inf where none does.  boxes: only the pairs whose leaf the walk can reach (reach(): a ray that lies
+    in the plane of a box face with a zero direction component there misses that box in the reference, whatever is inside)."""
+    if boxes:
+        n = o.shape[0]
+        tris = np.asarray(buf["triangles"], F).reshape(-1, 40)
+        lookup = np.asarray(buf["tri_lookup"], F)
+        lo_t = np.broadcast_to(np.asarray(tmin, F), (n,))
+        hi_t = np.broadcast_to(np.asarray(tmax, F), (n,))
+        best = np.full(n, np.inf, F)
+        for bi, (slots, mask) in reach(buf, o, d, hi_t).items():
+            if not slots.size:
+                continue
+            prims = np.array([min(u32f(lookup[s]), tris.shape[0] - 1) for s in slots], np.int64)
+            q = triangle_terms(np.asarray(buf["blas"], F).reshape(-1, 20)[bi], tris[prims], o, d)
+            ok = q["ok"] & mask & (q["t"] > lo_t[:, None]) & (q["t"] < hi_t[:, None])
+            best = np.minimum(best, np.where(ok, q["t"], np.inf).min(axis=1).astype(F))
+        return best
     blas = np.asarray(buf["blas"], F).reshape(-1, 20)
     tris = np.asarray(buf["triangles"], F).reshape(-1, 40)
     lookup = np.asarray(buf["tri_lookup"], F)
@@ -176,9 +304,24 @@ def brute_triangles(buf, o, d, tmin, tmax):
     return best
 
 
-def all_triangle_hits(buf, o, d):
+def all_triangle_hits(buf, o, d, boxes=False):
     """Every (ray, t, instance, prim) that passes hit_triangle's tests (RK:344-379) over every (triangle, instance) pair, in the
-    same float32 operations as brute_triangles; the limits are applied by k_smallest."""
+    same float32 operations as brute_triangles; the limits are applied by k_smallest.  boxes: as in brute_triangles, with the
+    reference's 9999 as the limit."""
+    if boxes:
+        tris = np.asarray(buf["triangles"], F).reshape(-1, 40)
+        lookup = np.asarray(buf["tri_lookup"], F)
+        out = [(np.zeros(0, np.int64), np.zeros(0, F), np.zeros(0, np.int64), np.zeros(0, np.int64))]
+        for bi, (slots, mask) in reach(buf, o, d, F(9999.0)).items():
+            if not slots.size:
+                continue
+            prim_of = np.array([min(u32f(lookup[s]), tris.shape[0] - 1) for s in slots], np.int64)
+            prims = np.unique(prim_of)
+            pm = np.stack([mask[:, prim_of == p].any(axis=1) for p in prims], axis=1)
+            q = triangle_terms(np.asarray(buf["blas"], F).reshape(-1, 20)[bi], tris[prims], o, d)
+            ray, tri = np.nonzero(q["ok"] & pm)
+            out.append((ray, q["t"][ray, tri], np.full(ray.size, bi), prims[tri]))
+        return tuple(np.concatenate(c) for c in zip(*out))
     blas = np.asarray(buf["blas"], F).reshape(-1, 20)
     tris = np.asarray(buf["triangles"], F).reshape(-1, 40)
     lookup = np.asarray(buf["tri_lookup"], F)
@@ -341,12 +484,14 @@ def _check_sphere_nearest(oracle, sp, o, d, h, tmin, tmax, ref=None):
     return int(hit.size)
 
 
-def check_all_queries(oracle, r, state, rays):
+def check_all_queries(oracle, r, state, rays, differ=differ, boxes=False):
     """Every query family of renderer `r` against the scene state the host holds now, bit for bit.  state: {"tri": the triangle
     buffers (tri_buffers(scene, mat))} or {"spheres": the (n, 8) records}, plus "params" (scene.pack_params of the renderer's
     maxBounces) and "faces" (the sky's); rays: (origins, directions), each (n, 3).  The shaded query and pick take the camera rays
     of the renderer's own frame (a shaded ray stands for a pixel only with the direction the frame itself forms).  Returns the
-    number of `rays` that hit."""
+    number of `rays` that hit.  differ: the rule float words are compared by (bits unless given); boxes: the brute forces count
+    only what the walk's box tests let it reach (brute_triangles)."""
+    same = lambda a, b: _same(a, b, differ)
     o, d = (np.ascontiguousarray(a, F) for a in rays)
     n = o.shape[0]
     params = np.asarray(state["params"], F)
@@ -358,7 +503,7 @@ def check_all_queries(oracle, r, state, rays):
     # trace_rays (the first call also carries the host's state to the context: recalculateScene)
     near = r.trace_rays(o, d)
     if tri:
-        hits = check_triangle_hits(oracle, buf, o, d, near)
+        hits = check_triangle_hits(oracle, buf, o, d, near, differ)
         first = oracle.trace_tri_rays(buf, o, d)
     else:
         with np.errstate(all="ignore"):
@@ -372,12 +517,12 @@ def check_all_queries(oracle, r, state, rays):
     found = lim["prim"] >= 0
     if tri:
         with np.errstate(all="ignore"):
-            best = brute_triangles(buf, o, d, tmin, tmax)
+            best = brute_triangles(buf, o, d, tmin, tmax, boxes)
             t, u, v, nrm = restate_triangle_hits(buf, o[found], d[found], lim["prim"][found], lim["instance"][found])
         assert np.array_equal(found, np.isfinite(best)), "the limited query and the brute force disagree on %d rays" % int(
             (found != np.isfinite(best)).sum())
         assert same(lim["t"], np.where(found, best, F(-1.0))), "limited t differs from the brute force on %d rays" % int(
-            (bits(lim["t"]) != bits(np.where(found, best, F(-1.0)))).sum())
+            differ(lim["t"], np.where(found, best, F(-1.0))).sum())
         assert same(t, lim["t"][found]) and same(u, lim["u"][found]) and same(v, lim["v"][found]) and same(nrm, lim["normal"][found])
         assert np.all(lim["instance"][~found] == -1) and np.all(lim["u"][~found] == 0) and np.all(lim["v"][~found] == 0)
         assert np.all(lim["normal"][~found] == 0) and np.all(lim["instance"][found] >= 0)
@@ -390,7 +535,7 @@ def check_all_queries(oracle, r, state, rays):
     # trace_rays_multi, k = 3 and 6 (the K = 4 and K = 8 lists below capacity): the brute force's k smallest, hit 0 the nearest query
     if tri:
         with np.errstate(all="ignore"):
-            cand = all_triangle_hits(buf, o, d)
+            cand = all_triangle_hits(buf, o, d, boxes)
     for k in (3, 6):
         h = host_multi(r, pack(o, d), 0, k)
         filled = h["prim"] >= 0
@@ -413,7 +558,7 @@ def check_all_queries(oracle, r, state, rays):
             I = np.full((n, k), -1, np.int32)
             assert np.all(h["u"] == 0) and np.all(h["v"] == 0)
             assert np.array_equal(h["prim"][:, 0], near["prim"])            # (the lowest index wins a tie in both)
-        bad = (h["prim"] != P) | (h["instance"] != I) | (bits(h["t"]) != bits(T))
+        bad = (h["prim"] != P) | (h["instance"] != I) | differ(h["t"], T)
         assert not bad.any(), "k = %d: the walk and the brute force differ on %d rays, first %s" % (
             k, int(bad.any(axis=1).sum()), np.nonzero(bad.any(axis=1))[0][:5])
         assert same(h["t"][:, 0], near["t"]) and np.array_equal(h["prim"][:, 0] >= 0, near["prim"] >= 0)
@@ -425,7 +570,7 @@ def check_all_queries(oracle, r, state, rays):
     else:
         ref_rgb = oracle.render(params, sp, state["faces"], W, H, want_float=True)[1]
     got = r.shade_rays(oc, dc, compose=True)
-    diff = (bits(got[:, 0:3]) != bits(ref_rgb.reshape(-1, 3))).any(axis=-1)
+    diff = differ(got[:, 0:3], ref_rgb.reshape(-1, 3)).any(axis=-1)
     assert not diff.any(), "%d of %d shaded camera rays differ from the oracle's float frame" % (int(diff.sum()), W * H)
     if not tri and sp.shape[0] == 0:                                # the empty scene: the sky along the ray as given, dist 0
         sky = shade_common.OracleRays(oracle, params, sp, state["faces"]).sky(dc[::7])
@@ -438,7 +583,7 @@ def check_all_queries(oracle, r, state, rays):
     dirs = np.stack([oracle.ray_dir(params, W, H, int(x), int(y)) for x, y in zip(xs, ys)])
     orig = np.broadcast_to(params[0:3], dirs.shape).astype(F)
     if tri:
-        check_triangle_hits(oracle, buf, orig, dirs, p)
+        check_triangle_hits(oracle, buf, orig, dirs, p, differ)
     else:
         _check_sphere_nearest(oracle, sp, orig, dirs, p, F(0.001), F(9999.0))
     return hits
