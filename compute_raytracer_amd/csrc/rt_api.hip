@@ -215,27 +215,26 @@ int rt_create(int device, rt_ctx** out) {
     c->wave_slots = (uint32_t)prop.multiProcessorCount * 20u;      // 4 SIMDs x 5 waves: the form of the triangle kernel that awaited frames -- the ones with a work list -- run (rt_launch_triangles)
     hipError_t err;
     err = hipSuccess;
-    for (int k = 0; k < kStreams && err == hipSuccess; ++k) err = hipStreamCreateWithFlags(&c->streams[k], hipStreamNonBlocking);
+    for (int k = 0; k < kStreams && err == hipSuccess; ++k) err = c->streams[k].ensure(hipStreamNonBlocking);
     c->stream = c->streams[0];
-    if (err == hipSuccess) err = hipEventCreateWithFlags(&c->ev_scene, hipEventDisableTiming);
-    if (err == hipSuccess) err = hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking);
-    for (int k = 0; k < kStreams && err == hipSuccess; ++k) err = hipEventCreateWithFlags(&c->ev_copy[k], hipEventDisableTiming);
+    if (err == hipSuccess) err = c->ev_scene.ensure(hipEventDisableTiming);
+    if (err == hipSuccess) err = c->copy_stream.ensure(hipStreamNonBlocking);
+    for (int k = 0; k < kStreams && err == hipSuccess; ++k) err = c->ev_copy[k].ensure(hipEventDisableTiming);
     for (int i = 0; i < RT355_MAX_IN_FLIGHT && err == hipSuccess; ++i) {
-        if ((err = hipEventCreate(&c->ev_prep0[i])) != hipSuccess) break;
-        if ((err = hipEventCreate(&c->ev_k0[i])) != hipSuccess) break;
-        if ((err = hipEventCreate(&c->ev_k1[i])) != hipSuccess) break;
-        err = hipEventCreateWithFlags(&c->ev_done[i], hipEventDisableTiming);
+        if ((err = c->ev_prep0[i].ensure()) != hipSuccess) break;
+        if ((err = c->ev_k0[i].ensure()) != hipSuccess) break;
+        if ((err = c->ev_k1[i].ensure()) != hipSuccess) break;
+        err = c->ev_done[i].ensure(hipEventDisableTiming);
     }
     if (err != hipSuccess ||
-        (err = hipMalloc(reinterpret_cast<void**>(&c->d_rays), kCtrlBytes * RT355_MAX_IN_FLIGHT)) != hipSuccess ||
-        (err = hipMemset(c->d_rays, 0, kCtrlBytes * RT355_MAX_IN_FLIGHT)) != hipSuccess ||
-        (err = hipHostMalloc(reinterpret_cast<void**>(&c->h_rays), 16u * RT355_MAX_IN_FLIGHT + 8u * kStreams,
-                             hipHostMallocDefault)) != hipSuccess) {
+        (err = c->d_rays.replace(kCtrlBytes * RT355_MAX_IN_FLIGHT)) != hipSuccess ||
+        (err = hipMemset(c->d_rays.p, 0, kCtrlBytes * RT355_MAX_IN_FLIGHT)) != hipSuccess ||
+        (err = c->h_rays.replace(16u * RT355_MAX_IN_FLIGHT + 8u * kStreams)) != hipSuccess) {
         rt_destroy(c);
         return fail_hip(err, "rt_create: stream/event/counter setup");
     }
-    std::memset(c->h_rays, 0, 16u * RT355_MAX_IN_FLIGHT + 8u * kStreams);
-    c->h_split = c->h_rays + 2u * RT355_MAX_IN_FLIGHT;
+    std::memset(c->h_rays.p, 0, 16u * RT355_MAX_IN_FLIGHT + 8u * kStreams);
+    c->h_split = c->h_rays.as<unsigned long long>() + 2u * RT355_MAX_IN_FLIGHT;
     // An event's FIRST record allocates its signal (~10 us each, measured through bench.py's first timed region: 0.25 ms for twelve
     // untouched slots): every event of the ring is recorded once here, so that a host's first frames do not pay for it one by one.
     for (int i = 0; i < RT355_MAX_IN_FLIGHT && err == hipSuccess; ++i) {
@@ -260,41 +259,11 @@ int rt_destroy(rt_ctx* c) {
     for (int k = 0; k < kStreams; ++k)
         if (c->streams[k]) (void)hipStreamSynchronize(c->streams[k]);
     if (c->query_pending) (void)hipEventSynchronize(c->ev_query);
-    if (c->query_stream) { (void)hipStreamSynchronize(c->query_stream); (void)hipStreamDestroy(c->query_stream); }
-    if (c->ev_query) (void)hipEventDestroy(c->ev_query);
-    if (c->copy_stream) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
-    for (int k = 0; k < kStreams; ++k)
-        if (c->ev_copy[k]) (void)hipEventDestroy(c->ev_copy[k]);
+    if (c->query_stream) (void)hipStreamSynchronize(c->query_stream);
+    if (c->copy_stream) (void)hipStreamSynchronize(c->copy_stream);
     rt_comm_release(c);
     delete c->rebuild;
-    c->rebuild = nullptr;
-    (void)hipFree(c->d_records);
-    (void)hipFree(c->d_scene);
-    for (int i = 0; i < 6; ++i) (void)hipFree(c->d_face[i]);
-    for (int k = 0; k < kStreams; ++k) (void)hipFree(c->d_outs[k]);
-    for (int k = 0; k < kStreams; ++k) (void)hipFree(c->d_fin[k]);
-    (void)hipFree(c->d_queue);
-    (void)hipFree(c->d_bvh_rec);
-    (void)hipFree(c->d_bvh_link);
-    for (rt_ctx::DevBuf* b : {&c->d_tri, &c->d_tri_lookup, &c->d_tex, &c->d_corners, &c->d_flow, &c->d_refit_plan, &c->d_build, &c->d_qrays, &c->d_qhits, &c->d_qxy})
-        (void)hipFree(b->p);
-    for (int k = 0; k < kStreams; ++k) { (void)hipFree(c->d_tile_cost[k].p); (void)hipFree(c->d_tile_order[k].p); }
-    for (int v = 0; v < kVersions; ++v)
-        for (rt_ctx::DevBuf* b : {&c->d_nodes[v], &c->d_blas[v], &c->d_blas_lookup[v]}) (void)hipFree(b->p);
-    (void)hipFree(c->d_rays);
-    if (c->h_rays) (void)hipHostFree(c->h_rays);
-    for (int i = 0; i < RT355_MAX_IN_FLIGHT; ++i) {
-        if (c->ev_prep0[i]) (void)hipEventDestroy(c->ev_prep0[i]);
-        if (c->ev_k0[i]) (void)hipEventDestroy(c->ev_k0[i]);
-        if (c->ev_k1[i]) (void)hipEventDestroy(c->ev_k1[i]);
-        if (c->ev_done[i]) (void)hipEventDestroy(c->ev_done[i]);
-    }
-    if (c->ev_scene) (void)hipEventDestroy(c->ev_scene);
-    for (int v = 0; v < kVersions; ++v)
-        if (c->ev_ver[v]) (void)hipEventDestroy(c->ev_ver[v]);
-    for (int k = 0; k < kStreams; ++k)
-        if (c->streams[k]) (void)hipStreamDestroy(c->streams[k]);
-    delete c;
+    delete c;                 // every buffer, event and stream: released by its owner (rt_own.h), in the order rt_ctx.h declares
     return RT_OK;
 }
 
@@ -332,18 +301,18 @@ static int ensure_out(rt_ctx* c) {
     // sized for the padded tile count so that the buffer can be an all-gather operand; one
     // buffer per stream rt_render rotates over (consecutive frames may overlap on the device)
     const size_t need = (size_t)rt_padded_tiles(c->H, c->world) * 8u * c->W * 4u;
-    if (need > c->out_bytes || !c->d_outs[0]) {
+    if (need > c->out_bytes || !c->d_outs[0].p) {
         RT_HIP(hipStreamSynchronize(c->stream));
-        for (int k = 0; k < kStreams; ++k) { (void)hipFree(c->d_outs[k]); c->d_outs[k] = nullptr; }
+        for (int k = 0; k < kStreams; ++k) c->d_outs[k].reset();
         c->d_out = nullptr;
         c->out_bytes = 0;
         if (need) {
             for (int k = 0; k < kStreams; ++k) {
-                RT_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_outs[k]), need));
-                RT_HIP(hipMemsetAsync(c->d_outs[k], 0, need, c->stream));
+                RT_HIP(c->d_outs[k].replace(need));
+                RT_HIP(hipMemsetAsync(c->d_outs[k].p, 0, need, c->stream));
             }
             RT_HIP(hipStreamSynchronize(c->stream));
-            c->d_out = c->d_outs[0];
+            c->d_out = c->d_outs[0].as<uint8_t>();
             c->out_bytes = need;
         }
     }
@@ -357,10 +326,8 @@ static int ensure_queue(rt_ctx* c) {
     const size_t entries = (size_t)rt_padded_tiles(c->H, c->world) * 8u * c->W;
     if (entries > c->queue_cap) {
         { int rc = drain(c); if (rc != RT_OK) return rc; }
-        (void)hipFree(c->d_queue);
-        c->d_queue = nullptr;
         c->queue_cap = 0;
-        RT_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_queue), entries * 3u * sizeof(float4)));
+        RT_HIP(c->d_queue.replace(entries * 3u * sizeof(float4)));
         c->queue_cap = entries;
     }
     return RT_OK;
@@ -370,12 +337,10 @@ static int ensure_queue(rt_ctx* c) {
 // frame that may be in flight on its own stream): allocated when a frame first needs them.
 static int ensure_fin(rt_ctx* c) {
     const size_t slots = (size_t)rt_padded_tiles(c->H, c->world) * 8u * c->W;
-    if (slots > c->fin_slots) {
+    if (slots * 2u * sizeof(float4) > c->d_fin[kStreams - 1].cap) {      // the last one allocated: all of them hold as much
         { int rc = drain(c); if (rc != RT_OK) return rc; }
-        for (int k = 0; k < kStreams; ++k) { (void)hipFree(c->d_fin[k]); c->d_fin[k] = nullptr; }
-        c->fin_slots = 0;
-        for (int k = 0; k < kStreams; ++k) RT_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_fin[k]), slots * 2u * sizeof(float4)));
-        c->fin_slots = slots;
+        for (int k = 0; k < kStreams; ++k) c->d_fin[k].reset();
+        for (int k = 0; k < kStreams; ++k) RT_HIP(c->d_fin[k].replace(slots * 2u * sizeof(float4)));
     }
     return RT_OK;
 }
@@ -422,16 +387,15 @@ int rt_write_spheres(rt_ctx* c, const float* records, uint32_t n) {
     { int rc = drain(c); if (rc != RT_OK) return rc; }
     if (n > c->cap_n) {
         RT_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_records); (void)hipFree(c->d_scene);
-        c->d_records = nullptr; c->d_scene = nullptr;
+        c->d_records.reset(); c->d_scene.reset();
         c->cap_n = 0;
         const size_t cap16 = ((size_t)n + 15u) & ~(size_t)15u;
-        RT_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_records), (size_t)n * 32u));
-        RT_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_scene), cap16 * 8u * sizeof(float4)));
+        RT_HIP(c->d_records.replace((size_t)n * 32u));
+        RT_HIP(c->d_scene.replace(cap16 * 8u * sizeof(float4)));
         c->cap_n = n;
     }
     if (n) {
-        RT_HIP(hipMemcpyAsync(c->d_records, records, (size_t)n * 32u, hipMemcpyHostToDevice, c->stream));
+        RT_HIP(hipMemcpyAsync(c->d_records.p, records, (size_t)n * 32u, hipMemcpyHostToDevice, c->stream));
         RT_HIP(hipStreamSynchronize(c->stream));   // caller may free `records` now (writeBuffer semantics)
     }
     c->n = n;
@@ -460,16 +424,14 @@ int rt_write_cubemap_face(rt_ctx* c, int face, uint32_t w, uint32_t h, const uin
     RT_HIP(hipSetDevice(c->device));
     { int rc = drain(c); if (rc != RT_OK) return rc; }
     const size_t bytes = (size_t)w * h * 4u;
-    if (c->fw[face] != w || c->fh[face] != h || !c->d_face[face]) {
+    if (c->fw[face] != w || c->fh[face] != h || !c->d_face[face].p) {
         RT_HIP(hipStreamSynchronize(c->stream));
-        (void)hipFree(c->d_face[face]);
-        c->d_face[face] = nullptr;
         c->fw[face] = c->fh[face] = 0;
-        RT_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_face[face]), bytes < 16 ? 16 : bytes));
+        RT_HIP(c->d_face[face].replace(bytes < 16 ? 16 : bytes));
         c->fw[face] = w;
         c->fh[face] = h;
     }
-    RT_HIP(hipMemcpyAsync(c->d_face[face], rgba, bytes, hipMemcpyHostToDevice, c->stream));
+    RT_HIP(hipMemcpyAsync(c->d_face[face].p, rgba, bytes, hipMemcpyHostToDevice, c->stream));
     RT_HIP(hipStreamSynchronize(c->stream));
     c->face_texel0[face] = (uint32_t)rgba[0] | ((uint32_t)rgba[1] << 8) | ((uint32_t)rgba[2] << 16);
     return RT_OK;
@@ -480,15 +442,14 @@ static int grow_buf(rt_ctx* c, rt_ctx::DevBuf& b, size_t need) {
     if (need <= b.cap) return RT_OK;
     { int rc = drain(c); if (rc != RT_OK) return rc; }
     RT_HIP(hipStreamSynchronize(c->stream));
-    void* np = nullptr;
+    rt_ctx::DevBuf nb;
     const size_t cap = need < 256 ? 256 : need;
-    RT_HIP(hipMalloc(&np, cap));
-    RT_HIP(hipMemsetAsync(np, 0, cap, c->stream));
-    if (b.p && b.used) RT_HIP(hipMemcpyAsync(np, b.p, b.used, hipMemcpyDeviceToDevice, c->stream));
+    RT_HIP(nb.replace(cap));
+    RT_HIP(hipMemsetAsync(nb.p, 0, cap, c->stream));
+    if (b.p && b.used) RT_HIP(hipMemcpyAsync(nb.p, b.p, b.used, hipMemcpyDeviceToDevice, c->stream));
     RT_HIP(hipStreamSynchronize(c->stream));
-    (void)hipFree(b.p);
-    b.p = np;
-    b.cap = cap;
+    nb.used = b.used;
+    b = std::move(nb);        // frees the old block
     return RT_OK;
 }
 
@@ -755,7 +716,7 @@ static int apply_version(rt_ctx* c, uint32_t v, uint32_t slot, hipStream_t s) {
     if (ia.n_blas_f) std::memcpy(ia.data + 31 * 8, c->inst.blas.data(), ia.n_blas_f * sizeof(float));
     if (ia.n_lookup_f) std::memcpy(ia.data + 31 * 8 + 16 * 20, c->inst.lookup.data(), ia.n_lookup_f * sizeof(float));
     RT_HIP(rt_launch_apply_instances(ia, s));
-    if (!c->ev_ver[v]) RT_HIP(hipEventCreateWithFlags(&c->ev_ver[v], hipEventDisableTiming));
+    RT_HIP(c->ev_ver[v].ensure(hipEventDisableTiming));
     RT_HIP(hipEventRecord(c->ev_ver[v], s));
     c->ver_stream[v] = s;
     c->ver_gen[v] = c->inst.gen;
@@ -791,7 +752,7 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
         return fail(RT_ERR_UNSUPPORTED, "rt_render: the heatmap kernel counts BVH traversal steps; sphere scenes have no BVH");
     }
     for (int i = 0; i < 6; ++i)
-        if (!c->d_face[i]) return fail(RT_ERR_STATE, "rt_render: all six cube map faces must be written first");
+        if (!c->d_face[i].p) return fail(RT_ERR_STATE, "rt_render: all six cube map faces must be written first");
     RT_HIP(hipSetDevice(c->device));
 
     // ---- which kernels render this frame ----
@@ -862,12 +823,10 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
             }
             c->rebuild->ready = false;
         }
-        if (nodes + 1u > c->bvh_cap) {
-            (void)hipFree(c->d_bvh_rec); (void)hipFree(c->d_bvh_link);
-            c->d_bvh_rec = nullptr; c->d_bvh_link = nullptr; c->bvh_cap = 0;
-            RT_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_bvh_rec), ((size_t)nodes + 1u) * sizeof(float4)));
-            RT_HIP(hipMalloc(reinterpret_cast<void**>(&c->d_bvh_link), ((size_t)nodes + 1u) * sizeof(uint32_t)));
-            c->bvh_cap = nodes + 1u;
+        if (((size_t)nodes + 1u) * sizeof(uint32_t) > c->d_bvh_link.cap) {      // the second of the pair: both hold as many nodes
+            c->d_bvh_rec.reset(); c->d_bvh_link.reset();
+            RT_HIP(c->d_bvh_rec.replace(((size_t)nodes + 1u) * sizeof(float4)));
+            RT_HIP(c->d_bvh_link.replace(((size_t)nodes + 1u) * sizeof(uint32_t)));
         }
         c->bvh_nodes = nodes;
     }
@@ -931,7 +890,7 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     fa.tile_first = c->rank; fa.tile_step = c->world; fa.n_local_tiles = local_tiles(c);
     fa.signed_filter = signed_filter;
     {
-        const float4* b = c->d_scene;
+        const float4* b = c->d_scene.as<float4>();
         const uint32_t m = c->n16;
         fa.geo = b; fa.lgt = b + m; fa.cam = b + 2u * m; fa.col = b + 3u * m;
         fa.geo_f = b + 4u * m; fa.lgt_f = b + 5u * m; fa.cam_f = b + 6u * m;
@@ -944,8 +903,8 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
         RtPrepArgs pa;
         std::memcpy(pa.p, c->params, sizeof pa.p);
         pa.N = c->n; pa.N16 = c->n16;
-        pa.records = c->d_records;
-        float4* b = c->d_scene;
+        pa.records = c->d_records.as<float>();
+        float4* b = c->d_scene.as<float4>();
         const uint32_t m = c->n16;
         pa.geo = b; pa.lgt = b + m; pa.cam = b + 2u * m; pa.col = b + 3u * m;
         pa.geo_f = b + 4u * m; pa.lgt_f = b + 5u * m; pa.cam_f = b + 6u * m;
@@ -958,22 +917,22 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     if (need_bvh) {
         if (upload_topology) {
             const size_t nn = (size_t)c->bvh_nodes + 1u;
-            RT_HIP(hipMemcpyAsync(c->d_bvh_rec, c->h_bvh_rec.data(), nn * sizeof(float4), hipMemcpyHostToDevice, s));
-            RT_HIP(hipMemcpyAsync(c->d_bvh_link, c->h_bvh_link.data(), nn * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+            RT_HIP(hipMemcpyAsync(c->d_bvh_rec.p, c->h_bvh_rec.data(), nn * sizeof(float4), hipMemcpyHostToDevice, s));
+            RT_HIP(hipMemcpyAsync(c->d_bvh_link.p, c->h_bvh_link.data(), nn * sizeof(uint32_t), hipMemcpyHostToDevice, s));
             RT_HIP(hipStreamSynchronize(s));   // pageable sources: the vectors may be rebuilt later
             c->bvh_topo_n = c->n;
         }
         // bounds of the inner nodes for the current positions (a topology from the worker was built for older ones)
-        if (refit) RT_HIP(rt_launch_bvh_refit(c->d_bvh_rec, c->d_bvh_link, c->bvh_nodes, c->d_records, s));
-        RT_HIP(rt_launch_bvh_fill(c->d_bvh_rec, c->d_bvh_link, c->bvh_nodes, fa.geo_f, s));
+        if (refit) RT_HIP(rt_launch_bvh_refit(c->d_bvh_rec.as<float4>(), c->d_bvh_link.as<uint32_t>(), c->bvh_nodes, c->d_records.as<float>(), s));
+        RT_HIP(rt_launch_bvh_fill(c->d_bvh_rec.as<float4>(), c->d_bvh_link.as<uint32_t>(), c->bvh_nodes, fa.geo_f, s));
         c->bvh_valid = true;
     }
     if (need_prep || need_bvh) {
         RT_HIP(hipEventRecord(c->ev_scene, s));
         c->scene_stream = s;
     }
-    fa.bvh_rec = use_bvh ? c->d_bvh_rec : nullptr;
-    fa.bvh_link = use_bvh ? c->d_bvh_link : nullptr;
+    fa.bvh_rec = use_bvh ? c->d_bvh_rec.as<float4>() : nullptr;
+    fa.bvh_link = use_bvh ? c->d_bvh_link.as<uint32_t>() : nullptr;
     fa.bvh_nodes = use_bvh ? c->bvh_nodes : 0u;
     // frames in flight on DIFFERENT streams run concurrently and share the chip: this frame's grid is
     // 1 / (number of distinct streams among it and the kStreams-1 frames enqueued before it)
@@ -998,17 +957,17 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
 
     // this frame's partial ray counters and its 32-byte control block: one of RT355_MAX_IN_FLIGHT
     // sets, all zeroed by rt_create and again by every frame's epilogue kernel (no memset or read-back by the host)
-    unsigned long long* counters = c->d_rays + (kCtrlBytes / 8u) * slot;
+    unsigned long long* counters = c->d_rays.as<unsigned long long>() + (kCtrlBytes / 8u) * slot;
     unsigned long long* ctrl = counters + kCounterBytes / 8u;
-    for (int i = 0; i < 6; ++i) { fa.face[i] = c->d_face[i]; fa.fw[i] = c->fw[i]; fa.fh[i] = c->fh[i]; }
+    for (int i = 0; i < 6; ++i) { fa.face[i] = c->d_face[i].as<uint8_t>(); fa.fw[i] = c->fw[i]; fa.fh[i] = c->fh[i]; }
     fa.sky_flat = sky_flat;
     fa.sky_seamless = sky_seamless;
     fa.out = dst;
     // one record buffer per frame that may be running: the frame kStreams slots back must be through with this one
-    fa.fin = resolve_pass ? c->d_fin[slot % (uint32_t)kStreams] : nullptr;
+    fa.fin = resolve_pass ? c->d_fin[slot % (uint32_t)kStreams].as<float4>() : nullptr;
     if (resolve_pass && slot >= (uint32_t)kStreams) RT_HIP(hipStreamWaitEvent(s, c->ev_k1[slot - (uint32_t)kStreams], 0));
     fa.rays = counters;
-    fa.queue = queue_pipeline ? c->d_queue : nullptr;   // rt_kernels.hip takes the pipeline only with a queue
+    fa.queue = queue_pipeline ? c->d_queue.as<float4>() : nullptr;   // rt_kernels.hip takes the pipeline only with a queue
     fa.qctrl = reinterpret_cast<uint32_t*>(ctrl) + 2;
     fa.queue_cap = queue_pipeline ? (uint32_t)c->queue_cap : 0u;
     const uint32_t v = slot % (uint32_t)kVersions;
@@ -1052,10 +1011,8 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
             RT_HIP(hipStreamSynchronize(s));
             const size_t cap = ((size_t)order_n * 4u + 7u) & ~(size_t)7u, scan_bytes = (size_t)rt_order_scan_words() * 4u;
             for (rt_ctx::DevBuf* b : {&c->d_tile_cost[order_set], &c->d_tile_order[order_set]}) {
-                (void)hipFree(b->p);
-                b->p = nullptr; b->cap = 0;
-                RT_HIP(hipMalloc(&b->p, cap + scan_bytes));                // the list carries two header words; behind the costs: order_tiles' bins
-                b->cap = cap;
+                RT_HIP(b->replace(cap + scan_bytes));                      // the list carries two header words; behind the costs: order_tiles' bins
+                b->cap = cap;                                              // ... which lie behind `cap`
             }
             RT_HIP(hipMemsetAsync(c->d_tile_cost[order_set].p, 0, cap + scan_bytes, s));   // tiles leave their times by atomicMax
             c->order_tiles[order_set] = 0;
@@ -1067,7 +1024,7 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
 #ifdef RT355_DEV_EXPORTS
         if (getenv("RT355_TRI_TIMELINE")) {
             const size_t words = 3u * ((size_t)order_n + 3u * 8192u + 15u * 256u + 64u + 8u * ((c->W + 7u) / 8u));
-            if (c->d_tri_dbg.cap < words * 8u) { (void)hipFree(c->d_tri_dbg.p); c->d_tri_dbg.p = nullptr; RT_HIP(hipMalloc(&c->d_tri_dbg.p, words * 8u)); c->d_tri_dbg.cap = words * 8u; }
+            if (c->d_tri_dbg.cap < words * 8u) RT_HIP(c->d_tri_dbg.replace(words * 8u));
             RT_HIP(hipMemsetAsync(c->d_tri_dbg.p, 0, c->d_tri_dbg.cap, s));
             ts.dbg = static_cast<unsigned long long*>(c->d_tri_dbg.p);
         }
@@ -1103,7 +1060,7 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     // that has to wake up first, and its turnaround (15-30 us) is what the work-list kernels behind the event hide in.  (Round 5
     // ran the epilogue inside order_hist's first workgroup to save a link of the chain: the host woke 11 us later and the frame
     // period GREW by as much -- TRI 0.276 -> 0.298 ms; profiles/r05/ref_awaited_trace.log.)
-    RT_HIP(rt_launch_frame_epilogue(counters, c->h_rays + 2u * slot, (uint32_t)(kCtrlBytes / 8u), s));
+    RT_HIP(rt_launch_frame_epilogue(counters, c->h_rays.as<unsigned long long>() + 2u * slot, (uint32_t)(kCtrlBytes / 8u), s));
     RT_HIP(hipEventRecord(c->ev_done[slot], s));
     if (order_set >= 0) {
         // after the frame's event: rt_wait does not wait for it, the stream's next frame does
@@ -1156,7 +1113,7 @@ int rt_render(rt_ctx* c) {
     // consecutive frames rotate over kStreams streams and colour buffers, so that frames enqueued
     // back to back overlap on the device; rt_read_pixels returns the latest one
     const uint32_t k = c->frames_rendered % (uint32_t)kStreams;
-    uint8_t* dst = c->d_outs[k];
+    uint8_t* dst = c->d_outs[k].as<uint8_t>();
     // The stream: the next of the four while frames are in flight (they overlap); the SAME one for a frame that follows an
     // awaited frame -- the reference's loop.  The work list of an awaited triangle frame is made from the previous frame of
     // its stream: rotating regardless, that was the frame four steps back, and with the instances turning (the reference's
@@ -1173,6 +1130,7 @@ int rt_render(rt_ctx* c) {
     // frame -- the de-interleave of the whole gathered frame, on the frame's own stream, moving its end event as rt_render_gather does
     if (rc == RT_OK)
         if (const char* e = getenv("RT355_DEV_ROOT_WORLD")) {
+            // raw on purpose: an owner with static storage duration would release them after the runtime has shut down
             static uint8_t* dev_gather[kStreams] = {nullptr};
             static uint8_t* dev_frame[kStreams] = {nullptr};
             const uint32_t world = (uint32_t)atoi(e);
@@ -1199,7 +1157,7 @@ void rt_abandon_in_flight(rt_ctx* c) {
     for (int k = 0; k < kStreams; ++k)
         if (c->streams[k]) (void)hipStreamSynchronize(c->streams[k]);
     if (c->in_flight) {
-        (void)hipMemsetAsync(c->d_rays, 0, kCtrlBytes * c->in_flight, c->stream);
+        (void)hipMemsetAsync(c->d_rays.p, 0, kCtrlBytes * c->in_flight, c->stream);
         (void)hipStreamSynchronize(c->stream);
     }
     (void)hipGetLastError();
@@ -1221,7 +1179,8 @@ int rt_wait(rt_ctx* c) {
     for (uint32_t i = 0; i < c->in_flight; ++i) RT_HIP(hipEventSynchronize(c->ev_done[i]));
     if (c->in_flight) {
         c->stats.frames += c->in_flight;
-        c->stats.rays = c->h_rays[2u * (c->in_flight - 1u)];       // of the latest frame
+        const unsigned long long* h_rays = c->h_rays.as<unsigned long long>();
+        c->stats.rays = h_rays[2u * (c->in_flight - 1u)];          // of the latest frame
         c->stats.batch_frames = c->in_flight;
         // Frames in flight?  Only the library's own rotation counts: a host that enqueues several frames on ONE stream
         // of its own (rt_render_to) has them serialised by that stream, and must not be given a quarter of the chip.
@@ -1248,7 +1207,7 @@ int rt_wait(rt_ctx* c) {
         for (int k = 0; k < kStreams; ++k) c->buf_slot[k] = -1;      // every frame of the batch is complete
         // a kernel that could not run as planned says so in the word behind its first ray counter (rt_device.h: report_fault)
         unsigned long long fault = 0ull;
-        for (uint32_t i = 0; i < c->stats.batch_frames; ++i) fault = std::max(fault, c->h_rays[2u * i + 1u]);
+        for (uint32_t i = 0; i < c->stats.batch_frames; ++i) fault = std::max(fault, h_rays[2u * i + 1u]);
         if (fault != 0ull) {
             char buf[160];
             std::snprintf(buf, sizeof buf, "rt_wait: the ray-trace kernel reported fault %llu (1: dynamic LDS not at address 0); the frame is incomplete", fault);
@@ -1286,13 +1245,13 @@ int rt_read_pixels_async(rt_ctx* c, uint32_t frames_back, uint8_t* dst, size_t c
     if (frames_back >= (uint32_t)kStreams || frames_back >= c->frames_rendered)
         return fail(RT_ERR_INVALID_ARG, "rt_read_pixels_async: frames_back must name one of the last four rt_render calls");
     if (c->world != 1u || c->comm) return fail(RT_ERR_STATE, "rt_read_pixels_async: whole-frame contexts only");
-    if (!c->d_outs[0]) return fail(RT_ERR_STATE, "rt_read_pixels_async: no colour buffer (rt_resize first)");
+    if (!c->d_outs[0].p) return fail(RT_ERR_STATE, "rt_read_pixels_async: no colour buffer (rt_resize first)");
     const size_t need = (size_t)c->H * c->W * 4u;
     if (cap < need) return fail(RT_ERR_CAPACITY, "rt_read_pixels_async: destination smaller than H * W * 4");
     RT_HIP(hipSetDevice(c->device));
     const uint32_t k = (c->frames_rendered - 1u - frames_back) % (uint32_t)kStreams;
     if (c->buf_slot[k] >= 0) RT_HIP(hipStreamWaitEvent(c->copy_stream, c->ev_k1[c->buf_slot[k]], 0));   // behind that frame's kernels
-    RT_HIP(hipMemcpyAsync(dst, c->d_outs[k], need, hipMemcpyDeviceToHost, c->copy_stream));
+    RT_HIP(hipMemcpyAsync(dst, c->d_outs[k].p, need, hipMemcpyDeviceToHost, c->copy_stream));
     RT_HIP(hipEventRecord(c->ev_copy[k], c->copy_stream));
     c->copy_pending[k] = true;
     return RT_OK;
@@ -1306,6 +1265,7 @@ int rt_read_pixels_wait(rt_ctx* c) {
     return RT_OK;
 }
 
+// raw on purpose: the memory is the caller's from here until rt_host_free
 int rt_host_alloc(size_t bytes, void** out) {
     if (!out || bytes == 0) return fail(RT_ERR_INVALID_ARG, "rt_host_alloc: NULL / zero size");
     *out = nullptr;
@@ -1384,9 +1344,10 @@ int rt_order_tiles(rt_ctx* c, const uint32_t* cost, uint32_t n, uint32_t wave_sl
     if (n == 0u) return RT_OK;
     RT_HIP(hipSetDevice(c->device));
     const size_t cost_bytes = ((size_t)n * 4u + 7u) & ~(size_t)7u, scan_bytes = (size_t)rt_order_scan_words() * 4u;
-    void *d_cost = nullptr, *d_order = nullptr;
-    hipError_t e = hipMalloc(&d_cost, cost_bytes + scan_bytes);
-    if (e == hipSuccess) e = hipMalloc(&d_order, ((size_t)n + 2u) * 4u);
+    rt_ctx::DevBuf cost_buf, order_buf;                 // temporaries of this call
+    hipError_t e = cost_buf.replace(cost_bytes + scan_bytes);
+    if (e == hipSuccess) e = order_buf.replace(((size_t)n + 2u) * 4u);
+    void *const d_cost = cost_buf.p, *const d_order = order_buf.p;
     if (e == hipSuccess) e = hipMemsetAsync(d_cost, 0, cost_bytes + scan_bytes, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_cost, cost, (size_t)n * 4u, hipMemcpyHostToDevice, c->stream);
     uint32_t* const scan = reinterpret_cast<uint32_t*>(static_cast<char*>(d_cost) + cost_bytes);
@@ -1398,8 +1359,6 @@ int rt_order_tiles(rt_ctx* c, const uint32_t* cost, uint32_t n, uint32_t wave_sl
     }
     if (e == hipSuccess) e = hipMemcpyAsync(order, d_order, ((size_t)n + 2u) * 4u, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    (void)hipFree(d_cost);
-    (void)hipFree(d_order);
     if (e != hipSuccess) return fail_hip(e, "rt_order_tiles");
     return RT_OK;
 }
@@ -1407,7 +1366,7 @@ int rt_order_tiles(rt_ctx* c, const uint32_t* cost, uint32_t n, uint32_t wave_sl
 int rt_read_hierarchy(rt_ctx* c, float* rec4, uint32_t* link, uint32_t cap_nodes, uint32_t* n_nodes) {
     if (!c || !n_nodes) return fail(RT_ERR_INVALID_ARG, "rt_read_hierarchy: NULL argument");
     *n_nodes = 0;
-    if (c->scene_kind != 0 || c->bvh_nodes == 0u || !c->d_bvh_rec || !c->d_bvh_link)
+    if (c->scene_kind != 0 || c->bvh_nodes == 0u || !c->d_bvh_rec.p || !c->d_bvh_link.p)
         return fail(RT_ERR_STATE, "rt_read_hierarchy: no frame of this sphere scene has walked a hierarchy");
     const uint32_t nodes = c->bvh_nodes;
     *n_nodes = nodes;
@@ -1415,8 +1374,8 @@ int rt_read_hierarchy(rt_ctx* c, float* rec4, uint32_t* link, uint32_t cap_nodes
     RT_HIP(hipSetDevice(c->device));
     { int rc = drain(c); if (rc != RT_OK) return rc; }
     const size_t nn = (size_t)nodes + 1u;
-    RT_HIP(hipMemcpyAsync(rec4, c->d_bvh_rec, nn * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
-    RT_HIP(hipMemcpyAsync(link, c->d_bvh_link, nn * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(hipMemcpyAsync(rec4, c->d_bvh_rec.p, nn * sizeof(float4), hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(hipMemcpyAsync(link, c->d_bvh_link.p, nn * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     RT_HIP(hipStreamSynchronize(c->stream));
     return RT_OK;
 }
@@ -1759,7 +1718,7 @@ static int query_prepare(rt_ctx* c, const char* who, hipStream_t s, bool& tri, R
     tri = c->scene_kind == 1;
     inst = 0;
     RT_HIP(hipSetDevice(c->device));
-    if (!c->ev_query) RT_HIP(hipEventCreateWithFlags(&c->ev_query, hipEventDisableTiming));
+    RT_HIP(c->ev_query.ensure(hipEventDisableTiming));
     if (tri) { int rc = ensure_corners(c, s); if (rc != RT_OK) return rc; }
     uint32_t v = 0;
     uint32_t root_meta[kInstMax] = {0};
@@ -1815,7 +1774,7 @@ struct Query {
 static int query_open(rt_ctx* c, const char* who, bool host, void* hip_stream, Query& q) {
     if (host) {
         RT_HIP(hipSetDevice(c->device));
-        if (!c->query_stream) RT_HIP(hipStreamCreateWithFlags(&c->query_stream, hipStreamNonBlocking));
+        RT_HIP(c->query_stream.ensure(hipStreamNonBlocking));
         q.s = c->query_stream;
     } else {
         q.s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
@@ -1842,11 +1801,7 @@ static int query_run(rt_ctx* c, const char* who, void* hip_stream, LAUNCH launch
 // a staging buffer of the host-memory queries (synchronous: idle between calls): grows, contents not kept
 static int grow_staging(rt_ctx::DevBuf& b, size_t need) {
     if (need <= b.cap) return RT_OK;
-    (void)hipFree(b.p);
-    b.p = nullptr; b.cap = 0;
-    const size_t cap = std::max(need, (size_t)65536u);
-    RT_HIP(hipMalloc(&b.p, cap));
-    b.cap = cap;
+    RT_HIP(b.replace(std::max(need, (size_t)65536u)));
     return RT_OK;
 }
 
@@ -1922,10 +1877,10 @@ static int query_launch(rt_ctx* c, const float4* rays, void* out, uint32_t n, co
     if (!flags && !any) {
         float4* hits = static_cast<float4*>(out);
         if (q.tri) RT_HIP(rt_launch_query_triangles(q.ts, q.inst, rays, hits, n, q.s));
-        else RT_HIP(rt_launch_query_spheres(c->d_records, c->n, rays, hits, n, q.s));
+        else RT_HIP(rt_launch_query_spheres(c->d_records.as<float>(), c->n, rays, hits, n, q.s));
     } else {
         if (q.tri) RT_HIP(rt_launch_limited_triangles(q.ts, q.inst, rays, flags, any, out, n, q.s));
-        else RT_HIP(rt_launch_limited_spheres(c->d_records, c->n, rays, flags, any, out, n, q.s));
+        else RT_HIP(rt_launch_limited_spheres(c->d_records.as<float>(), c->n, rays, flags, any, out, n, q.s));
     }
     return RT_OK;
 }
@@ -1979,7 +1934,7 @@ static int multi_check(const char* who, rt_ctx* c, const float* rays, uint32_t n
 
 static int multi_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flags, uint32_t k, float4* hits, const Query& q) {
     if (q.tri) RT_HIP(rt_launch_multi_triangles(q.ts, q.inst, rays, flags, k, hits, n, q.s));
-    else RT_HIP(rt_launch_multi_spheres(c->d_records, c->n, rays, flags, k, hits, n, q.s));
+    else RT_HIP(rt_launch_multi_spheres(c->d_records.as<float>(), c->n, rays, flags, k, hits, n, q.s));
     return RT_OK;
 }
 
@@ -2028,7 +1983,7 @@ static int shade_state(const char* who, rt_ctx* c) {
     char msg[160];
     if (!c->have_params) { std::snprintf(msg, sizeof msg, "%s: rt_write_params has not been called", who); return fail(RT_ERR_STATE, msg); }
     for (int i = 0; i < 6; ++i)
-        if (!c->d_face[i]) { std::snprintf(msg, sizeof msg, "%s: all six cube map faces must be written first", who); return fail(RT_ERR_STATE, msg); }
+        if (!c->d_face[i].p) { std::snprintf(msg, sizeof msg, "%s: all six cube map faces must be written first", who); return fail(RT_ERR_STATE, msg); }
     if (c->scene_kind == 1 && c->d_tri.used && !c->d_tex.used) {   // meshTex is mandatory in the reference (RR:113-114); default: 1x1 white
         const uint8_t white[4] = {255, 255, 255, 255};
         int rc = rt_write_mesh_texture(c, 1, 1, white);
@@ -2048,7 +2003,7 @@ static int shade_check(const char* who, rt_ctx* c, const float* rays, uint32_t n
 // by value -- no slot of the event ring, no counters, no field of the stats.
 static void shade_frame_args(const rt_ctx* c, uint32_t W, uint32_t H, RtFrameArgs& fa) {
     camera_frame_args(c, W, H, fa);
-    for (int i = 0; i < 6; ++i) { fa.face[i] = c->d_face[i]; fa.fw[i] = c->fw[i]; fa.fh[i] = c->fh[i]; }
+    for (int i = 0; i < 6; ++i) { fa.face[i] = c->d_face[i].as<uint8_t>(); fa.fw[i] = c->fw[i]; fa.fh[i] = c->fh[i]; }
     sky_flags(c, fa.sky_flat, fa.sky_seamless);
 }
 // The shade kernel on q.s behind query_prepare (rays have no frame: W = H = 0)
@@ -2056,7 +2011,7 @@ static int shade_launch(rt_ctx* c, const float4* rays, uint32_t n, uint32_t flag
     RtFrameArgs fa;
     shade_frame_args(c, 0u, 0u, fa);
     if (q.tri) RT_HIP(rt_launch_shade_triangles(fa, q.ts, q.inst, rays, flags, out, n, q.s));
-    else RT_HIP(rt_launch_shade_spheres(fa, c->d_records, c->n, rays, flags, out, n, q.s));
+    else RT_HIP(rt_launch_shade_spheres(fa, c->d_records.as<float>(), c->n, rays, flags, out, n, q.s));
     return RT_OK;
 }
 
@@ -2110,7 +2065,7 @@ static int sample_launch(rt_ctx* c, uint32_t ss, uint8_t* rgba8, float* rgbaf, c
     shade_frame_args(c, ss * c->W, ss * c->H, fa);
     const RtSampleOut o = {c->W, c->H, ss, reinterpret_cast<uint32_t*>(rgba8), reinterpret_cast<float4*>(rgbaf)};
     if (q.tri) RT_HIP(rt_launch_sample_triangles(fa, q.ts, q.inst, o, q.s));
-    else RT_HIP(rt_launch_sample_spheres(fa, c->d_records, c->n, o, q.s));
+    else RT_HIP(rt_launch_sample_spheres(fa, c->d_records.as<float>(), c->n, o, q.s));
     return RT_OK;
 }
 
@@ -2182,7 +2137,7 @@ static int gbuffer_launch(rt_ctx* c, const RtGbufferOut& o, const Query& q) {
     RtFrameArgs fa;
     camera_frame_args(c, c->W, c->H, fa);
     if (q.tri) RT_HIP(rt_launch_gbuffer_triangles(fa, q.ts, q.inst, o, q.s));
-    else RT_HIP(rt_launch_gbuffer_spheres(fa, c->d_records, c->n, o, q.s));
+    else RT_HIP(rt_launch_gbuffer_spheres(fa, c->d_records.as<float>(), c->n, o, q.s));
     return RT_OK;
 }
 
@@ -2235,7 +2190,7 @@ static int ao_launch(rt_ctx* c, const RtAoOut& o, const Query& q) {
     RtFrameArgs fa;
     camera_frame_args(c, c->W, c->H, fa);
     if (q.tri) RT_HIP(rt_launch_ao_triangles(fa, q.ts, q.inst, o, q.s));
-    else RT_HIP(rt_launch_ao_spheres(fa, c->d_records, c->n, o, q.s));
+    else RT_HIP(rt_launch_ao_spheres(fa, c->d_records.as<float>(), c->n, o, q.s));
     return RT_OK;
 }
 

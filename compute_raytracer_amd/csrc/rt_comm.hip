@@ -29,16 +29,17 @@
 
 static_assert(kExchangeStreams == (uint32_t)kStreams, "rt_exchange_plan.h and rt_ctx.h must agree on the number of streams");
 
-struct rt_comm_state {
+// Owns its events and buffers as rt_ctx does (rt_own.h): events declared first, so that `delete s` frees the buffers first.
+struct RT_INTERNAL rt_comm_state {
     ncclComm_t comm = nullptr;
     bool owns_comm = true;                 // false: the communicator belongs to an rt_group
-    uint8_t* d_gather[kStreams] = {nullptr};   // [world][padded_tiles][8][W][4], on ranks that receive
-    uint8_t* d_frame[kStreams] = {nullptr};    // [H][W][4], on ranks that receive
-    size_t gather_bytes = 0, frame_bytes = 0;
+    Event ev_r1[RT355_MAX_IN_FLIGHT];      // end of the render, before the exchange
+    Event ev_x1[RT355_MAX_IN_FLIGHT];      // end of the exchange, before the de-interleave
+    DevBuf d_gather[kStreams];             // [world][padded_tiles][8][W][4], on ranks that receive
+    DevBuf d_frame[kStreams];              // [H][W][4], on ranks that receive; allocated together with d_gather, set by set: the
+                                           // caps of the last set are the capacity of all
     int latest = -1;                       // buffer set of the latest rt_render_gather (-1: none yet)
     bool latest_has_frame = false;         // this rank received that frame
-    hipEvent_t ev_r1[RT355_MAX_IN_FLIGHT] = {nullptr};   // end of the render, before the exchange
-    hipEvent_t ev_x1[RT355_MAX_IN_FLIGHT] = {nullptr};   // end of the exchange, before the de-interleave
     bool slot_gathered[RT355_MAX_IN_FLIGHT] = {false};
     uint32_t latest_w = 0, latest_h = 0;   // target size the latest frame was assembled for
     // failure handling: a call that failed half way, an asynchronous RCCL error or a missed deadline leaves the
@@ -65,13 +66,11 @@ static size_t message_bytes(const rt_ctx* c) { return rt_plan_message_bytes(c->W
 static void free_buffers(rt_ctx* c) {
     rt_comm_state* s = c->comm;
     // rt_read_pixels / rt_device_pixels may be pointing into a gather buffer (the root renders straight into its slot)
-    for (int k = 0; k < kStreams; ++k)
-        if (s->d_gather[k] && c->d_out >= s->d_gather[k] && c->d_out < s->d_gather[k] + s->gather_bytes) c->d_out = c->d_outs[0];
     for (int k = 0; k < kStreams; ++k) {
-        (void)hipFree(s->d_gather[k]); s->d_gather[k] = nullptr;
-        (void)hipFree(s->d_frame[k]); s->d_frame[k] = nullptr;
+        const uint8_t* g = s->d_gather[k].as<uint8_t>();
+        if (g && c->d_out >= g && c->d_out < g + s->d_gather[k].cap) c->d_out = c->d_outs[0].as<uint8_t>();
     }
-    s->gather_bytes = s->frame_bytes = 0;
+    for (int k = 0; k < kStreams; ++k) { s->d_gather[k].reset(); s->d_frame[k].reset(); }
     s->latest = -1;
     s->latest_has_frame = false;
 }
@@ -79,11 +78,7 @@ static void free_buffers(rt_ctx* c) {
 void rt_comm_release(rt_ctx* c) {
     rt_comm_state* s = c->comm;
     if (!s) return;
-    free_buffers(c);
-    for (int i = 0; i < RT355_MAX_IN_FLIGHT; ++i)
-        if (s->ev_r1[i]) (void)hipEventDestroy(s->ev_r1[i]);
-    for (int i = 0; i < RT355_MAX_IN_FLIGHT; ++i)
-        if (s->ev_x1[i]) (void)hipEventDestroy(s->ev_x1[i]);
+    free_buffers(c);              // the d_out fix-up
     if (s->comm && s->owns_comm) (void)ncclCommDestroy(s->comm);
     delete s;
     c->comm = nullptr;
@@ -168,8 +163,8 @@ static int attach(rt_ctx* c, ncclComm_t comm, bool owns, uint32_t rank, uint32_t
     s->comm = comm;
     s->owns_comm = owns;
     for (int i = 0; i < RT355_MAX_IN_FLIGHT; ++i) {
-        hipError_t e = hipEventCreate(&s->ev_r1[i]);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_x1[i], hipEventDisableTiming);
+        hipError_t e = s->ev_r1[i].ensure();
+        if (e == hipSuccess) e = s->ev_x1[i].ensure(hipEventDisableTiming);
         if (e != hipSuccess) {
             c->comm = s;
             rt_comm_release(c);
@@ -187,17 +182,15 @@ static int ensure_buffers(rt_ctx* c, bool receives) {
     rt_comm_state* s = c->comm;
     if (!receives) return RT_OK;
     const size_t gb = message_bytes(c) * c->world, fb = (size_t)c->H * c->W * 4u;
-    if (gb <= s->gather_bytes && fb <= s->frame_bytes && s->d_gather[0] && s->d_frame[0]) return RT_OK;
+    if (gb <= s->d_gather[kStreams - 1].cap && fb <= s->d_frame[kStreams - 1].cap && s->d_gather[0].p && s->d_frame[0].p) return RT_OK;
     { int rc = rt_drain(c); if (rc != RT_OK) return rc; }
     free_buffers(c);
     for (int k = 0; k < kStreams; ++k) {
-        RT_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_gather[k]), gb));
-        RT_HIP(hipMalloc(reinterpret_cast<void**>(&s->d_frame[k]), fb));
-        RT_HIP(hipMemsetAsync(s->d_gather[k], 0, gb, c->stream));
+        RT_HIP(s->d_gather[k].replace(gb));
+        RT_HIP(s->d_frame[k].replace(fb));
+        RT_HIP(hipMemsetAsync(s->d_gather[k].p, 0, gb, c->stream));
     }
     RT_HIP(hipStreamSynchronize(c->stream));
-    s->gather_bytes = gb;
-    s->frame_bytes = fb;
     return RT_OK;
 }
 
@@ -208,7 +201,7 @@ static int render_part(rt_ctx* c, int root, uint32_t k, uint8_t** part) {
     rt_comm_state* s = c->comm;
     const RtXPlan plan = rt_exchange_plan(c->W, c->H, c->rank, c->world, root);
     { int rc = ensure_buffers(c, plan.receives); if (rc != RT_OK) return rc; }
-    *part = plan.part_in_gather ? s->d_gather[k] + plan.part_offset : c->d_outs[k];
+    *part = plan.part_in_gather ? s->d_gather[k].as<uint8_t>() + plan.part_offset : c->d_outs[k].as<uint8_t>();
     if (!*part) return fail(RT_ERR_STATE, "rt_render_gather: rt_resize has not been called");
     if (!plan.part_in_gather) { int rc = rt_order_colour_buffer(c, k, c->streams[k]); if (rc != RT_OK) return rc; }
     int rc = rt_enqueue(c, *part, c->streams[k]);
@@ -237,9 +230,9 @@ static int exchange_part(rt_ctx* c, int root, uint32_t k, uint8_t* part) {
     const RtXPlan plan = rt_exchange_plan(c->W, c->H, c->rank, c->world, root);
     for (const RtXOp& op : plan.ops) {
         if (op.kind == RtXKind::AllGather)
-            RT_NCCL(ncclAllGather(s->d_gather[k] + op.gather_offset, s->d_gather[k], op.bytes, ncclUint8, s->comm, st));   // in place: part = recv + rank * msg
+            RT_NCCL(ncclAllGather(s->d_gather[k].as<uint8_t>() + op.gather_offset, s->d_gather[k].p, op.bytes, ncclUint8, s->comm, st));   // in place: part = recv + rank * msg
         else if (op.kind == RtXKind::Recv)
-            RT_NCCL(ncclRecv(s->d_gather[k] + op.gather_offset, op.bytes, ncclUint8, (int)op.peer, s->comm, st));
+            RT_NCCL(ncclRecv(s->d_gather[k].as<uint8_t>() + op.gather_offset, op.bytes, ncclUint8, (int)op.peer, s->comm, st));
         else
             RT_NCCL(ncclSend(part, op.bytes, ncclUint8, (int)op.peer, s->comm, st));
     }
@@ -257,7 +250,7 @@ static int finish_part(rt_ctx* c, int root, uint32_t k, uint8_t* part) {
     // in rt_read_frame) was built and measured too: the copies are PCIe-bound either way, and eight strided ones are slower than
     // this kernel + one linear copy (0.667 against 0.589 ms per frame read).  So it stays here.
     if (receives)
-        RT_HIP(rt_launch_assemble(s->d_gather[k], s->d_frame[k], c->W, c->H, c->world, rt_padded_tiles(c->H, c->world), st));
+        RT_HIP(rt_launch_assemble(s->d_gather[k].as<uint8_t>(), s->d_frame[k].as<uint8_t>(), c->W, c->H, c->world, rt_padded_tiles(c->H, c->world), st));
     // the frame is complete when the exchange and the de-interleave are: move the slot's end event
     RT_HIP(hipEventRecord(c->ev_k1[c->in_flight - 1u], st));
     s->latest = (int)k;
@@ -314,8 +307,8 @@ int rt_comm_destroy(rt_ctx* c) {
     if (!c->comm->owns_comm) return fail(RT_ERR_STATE, "rt_comm_destroy: the communicator belongs to an rt_group");
     RT_HIP(hipSetDevice(c->device));
     { int rc = rt_drain(c); if (rc != RT_OK) return rc; }
-    c->d_out = c->d_outs[0];
-    c->out_bytes = c->d_outs[0] ? c->out_bytes : 0;
+    c->d_out = c->d_outs[0].as<uint8_t>();
+    c->out_bytes = c->d_outs[0].p ? c->out_bytes : 0;
     rt_comm_release(c);
     return rt_set_partition(c, 0, 1);
 }
@@ -364,9 +357,9 @@ int rt_frame_pixels(rt_ctx* c, void** out_ptr, size_t* out_bytes) {
     if (!c || !out_ptr || !out_bytes) return fail(RT_ERR_INVALID_ARG, "rt_frame_pixels: NULL argument");
     if (!c->comm || c->comm->latest < 0) return fail(RT_ERR_STATE, "rt_frame_pixels: no rt_render_gather yet");
     if (!c->comm->latest_has_frame) return fail(RT_ERR_STATE, "rt_frame_pixels: this rank did not receive the frame (it is not the root)");
-    if (c->comm->latest_w != c->W || c->comm->latest_h != c->H || (size_t)c->H * c->W * 4u > c->comm->frame_bytes)
+    if (c->comm->latest_w != c->W || c->comm->latest_h != c->H || (size_t)c->H * c->W * 4u > c->comm->d_frame[c->comm->latest].cap)
         return fail(RT_ERR_STATE, "rt_frame_pixels: the target was resized after the latest rt_render_gather");
-    *out_ptr = c->comm->d_frame[c->comm->latest];
+    *out_ptr = c->comm->d_frame[c->comm->latest].p;
     *out_bytes = (size_t)c->H * c->W * 4u;
     return RT_OK;
 }

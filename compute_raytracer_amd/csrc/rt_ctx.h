@@ -5,6 +5,7 @@
 #include "rt_types.h"
 #include "rt_tri_types.h"
 #include "rt_flow_build.h"
+#include "rt_own.h"
 
 #include <cstdio>
 #include <string>
@@ -43,15 +44,28 @@ constexpr size_t kCtrlBytes = kCounterBytes + 32u;                              
 
 struct rt_comm_state;   // rt_comm.hip
 
+// Ownership (rt_own.h): every device buffer, pinned buffer, event and stream below is a DevBuf, PinnedBuf, Event or Stream, and
+// `delete c` releases it -- rt_destroy names none of them.  Members are destroyed in reverse order of declaration, so the
+// streams are declared first, the events next and the buffers after them: buffers go first, then events, streams last, as
+// rt_destroy released them by hand.  A raw hipStream_t / hipEvent_t / pointer member owns nothing: it names one of these.
 struct rt_ctx {
+    using DevBuf = ::DevBuf;
     int device = 0;
+    // ---- streams (destroyed last) ----
+    Stream streams[kStreams];            // rt_render rotates: consecutive frames may overlap on the device
+    Stream copy_stream;                  // streaming read-back (rt_read_pixels_async)
+    Stream query_stream;                 // the host-memory ray queries, made at their first use
     hipStream_t stream = nullptr;        // uploads, read-back, and frames 0, 3, 6 ... of rt_render (= streams[0])
-    hipStream_t streams[kStreams] = {nullptr};   // rt_render rotates: consecutive frames may overlap on the device
-    hipEvent_t ev_prep0[RT355_MAX_IN_FLIGHT] = {nullptr}, ev_k0[RT355_MAX_IN_FLIGHT] = {nullptr},
-               ev_k1[RT355_MAX_IN_FLIGHT] = {nullptr};
-    hipEvent_t ev_done[RT355_MAX_IN_FLIGHT] = {nullptr};          // behind the frame's epilogue kernel: what rt_wait waits for
-    hipEvent_t ev_scene = nullptr;       // the scene arrays / hierarchy a frame reads are complete ...
+    // ---- events (destroyed before the streams) ----
+    Event ev_prep0[RT355_MAX_IN_FLIGHT], ev_k0[RT355_MAX_IN_FLIGHT], ev_k1[RT355_MAX_IN_FLIGHT];
+    Event ev_done[RT355_MAX_IN_FLIGHT];  // behind the frame's epilogue kernel: what rt_wait waits for
+    Event ev_scene;                      // the scene arrays / hierarchy a frame reads are complete ...
     hipStream_t scene_stream = nullptr;  // ... recorded on this stream
+    Event ev_copy[kStreams];             // per colour buffer: the last streaming copy out of it
+    Event ev_ver[kVersions];             // behind the apply_instances kernel that last brought the version up to date (made at first use) ...
+    hipStream_t ver_stream[kVersions] = {nullptr};   // ... on this stream
+    Event ev_query;                      // behind the latest ray query on any stream (made at first use)
+    // ---- state and buffers (the buffers are destroyed first) ----
     uint32_t in_flight = 0;              // frames enqueued since the last rt_wait
     hipStream_t slot_stream[RT355_MAX_IN_FLIGHT] = {nullptr};   // the stream each of them was enqueued on
     uint32_t frames_rendered = 0;        // rt_render calls: selects the colour buffer
@@ -64,10 +78,10 @@ struct rt_ctx {
     bool have_params = false;
     bool prep_spheres_valid = false;     // prep_spheres ran since the last rt_write_spheres
     bool prep_params_valid = false;      // ... and since the last rt_write_params (camera / light records)
-    float* d_records = nullptr;
-    uint32_t n = 0, cap_n = 0;
+    DevBuf d_records;                    // n x 32 B as written
+    uint32_t n = 0, cap_n = 0;           // cap_n: spheres d_records AND d_scene both hold (0 until both allocations succeeded)
     bool have_spheres = false;
-    float4* d_scene = nullptr;           // 8 float4 arrays of n16: geo lgt cam col geo_f lgt_f cam_f + {geo_w,lgt_w,cam_w,-}
+    DevBuf d_scene;                      // 8 float4 arrays of n16: geo lgt cam col geo_f lgt_f cam_f + {geo_w,lgt_w,cam_w,-}
     uint32_t n16 = 0;                    // n rounded up to a multiple of 16
     float scene_bound = 0.0f;            // max over spheres of |center| + radius (host side)
     double scene_min_radius = 0.0;       // smallest non-zero |radius| (rt_plan: the rescaled sign-aware test)
@@ -76,41 +90,37 @@ struct rt_ctx {
     std::vector<float> h_records;
     std::vector<float> h_bvh_rec;
     std::vector<uint32_t> h_bvh_link;
-    float4* d_bvh_rec = nullptr;
-    uint32_t* d_bvh_link = nullptr;
-    uint32_t bvh_cap = 0, bvh_nodes = 0;
+    DevBuf d_bvh_rec, d_bvh_link;        // float4 and uint32_t per node; allocated together, the link array last: its cap is the capacity of both
+    uint32_t bvh_nodes = 0;
     bool bvh_valid = false;              // the device records bound the current spheres
     uint32_t bvh_topo_n = 0;             // sphere count the device topology (links, leaf ids) was built for; 0: none
     struct rt_rebuild* rebuild = nullptr;   // worker thread that rebuilds the topology for moved spheres (rt_api.hip)
-    uint8_t* d_face[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    DevBuf d_face[6];
     uint32_t fw[6] = {0, 0, 0, 0, 0, 0}, fh[6] = {0, 0, 0, 0, 0, 0};
     uint32_t face_texel0[6] = {0, 0, 0, 0, 0, 0};   // first texel (rgb) of each face: a one-texel sky of one colour is "flat"
-    uint8_t* d_out = nullptr;              // colour buffer of the LATEST rt_render (one of d_outs)
-    uint8_t* d_outs[kStreams] = {nullptr};
-    // streaming read-back (rt_read_pixels_async): a copy stream, per colour buffer the event of the last copy out of it and the
+    uint8_t* d_out = nullptr;              // colour buffer of the LATEST rt_render: points into d_outs or into a gather buffer, owns nothing
+    DevBuf d_outs[kStreams];
+    // streaming read-back (rt_read_pixels_async): copy_stream, per colour buffer ev_copy and the
     // event slot of the frame of the current batch that renders into it (-1: none in flight)
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t ev_copy[kStreams] = {nullptr};
     bool copy_pending[kStreams] = {false};
     int buf_slot[kStreams] = {-1, -1, -1, -1};
-    float4* d_fin[kStreams] = {nullptr};         // end-of-path records of frames with a textured sky (rt_bvh.hip: sky_resolve), lazily
-    size_t fin_slots = 0;                        // pixel slots each of them holds
-    size_t out_bytes = 0;
+    DevBuf d_fin[kStreams];                      // end-of-path records of frames with a textured sky (rt_bvh.hip: sky_resolve), lazily;
+                                                 // allocated together, the last one last: its cap is the capacity of each
+    size_t out_bytes = 0;                        // bytes of each of d_outs once all are allocated and zeroed (rt_device_pixels reports it)
     // per frame in flight: RT_RAY_COUNTERS partial ray counters (kCtrlBytes - 32 bytes), then a 32-byte
     // control block: unused u64, queue count, queue head, pixel / tile-pair cursor
-    unsigned long long* d_rays = nullptr;
-    float4* d_queue = nullptr;             // path queue of the two-kernel pipeline
-    size_t queue_cap = 0;                  // entries
-    unsigned long long* h_split = nullptr; // behind h_rays, per stream: the number of tiles the stream's current work list renders in parts (order_hist writes it)
-    unsigned long long* h_rays = nullptr;  // pinned, device-visible: per frame in flight {rays, fault word}, written by the frame's epilogue kernel
+    DevBuf d_rays;
+    DevBuf d_queue;                        // path queue of the two-kernel pipeline
+    size_t queue_cap = 0;                  // entries (48 B each): what a frame's arguments carry
+    unsigned long long* h_split = nullptr; // behind h_rays (points into it), per stream: the number of tiles the stream's current work list renders in parts (order_hist writes it)
+    PinnedBuf h_rays;                      // pinned, device-visible: per frame in flight {rays, fault word}, written by the frame's epilogue kernel
     // the reference's triangle scene (RR:169-229), device copies in the reference's byte layouts
-    struct DevBuf { void* p = nullptr; size_t cap = 0; size_t used = 0; };
     DevBuf d_tri, d_tri_lookup, d_tex;
     DevBuf d_corners;                            // 48 B per lookup slot: the corners hitTriangle reads, in lookup order (tri_corners)
     bool corners_valid = false;                  // ... built since the last rt_write_triangles / rt_write_tri_lookup
     // Tile order of the triangle kernel (rt_triangles.hip: order_tiles), one set per stream of rt_render: the time every
     // tile of the stream's last frame took, and the longest-first permutation made of it for the stream's next frame.
-    DevBuf d_tile_cost[kStreams], d_tile_order[kStreams];
+    DevBuf d_tile_cost[kStreams], d_tile_order[kStreams];   // cap: the bytes of the costs / the list; order_tiles' scan words lie behind them
     uint32_t wave_slots = 4096;                      // waves of the triangle kernel the device holds at once
     uint32_t order_tiles[kStreams] = {0, 0, 0, 0};   // tile count d_tile_order[k] is a permutation of (0: none yet)
     // The buffers the reference rewrites before every frame (RR:169-192: BLAS records, BLAS lookup, the TLAS nodes at
@@ -125,8 +135,6 @@ struct rt_ctx {
     } inst;
     uint64_t inst_gen_carried = 0;               // inst.gen the last frame of a small form took along in its arguments (rt_stats.instance_uploads)
     uint64_t ver_gen[kVersions] = {0, 0, 0, 0};  // inst.gen each device version holds
-    hipEvent_t ev_ver[kVersions] = {nullptr};    // behind the apply_instances kernel that last brought the version up to date ...
-    hipStream_t ver_stream[kVersions] = {nullptr};   // ... on this stream
     size_t nodes_used = 0;                       // bytes of the node buffer written so far (any version)
     uint32_t node_count_max = 0;                 // largest u32(primitiveCount) of any node written so far (packed BLAS stack: <= 65535)
     // The triangle kernel reads the BLAS trees from the library's relinked copy (rt_flow_build.h: pair records) where the scene
@@ -154,11 +162,9 @@ struct rt_ctx {
     DevBuf d_refit_plan;
     DevBuf d_build;                              // scratch of rt_build_blas (rt_build.h: RtBuildArgs), kept between calls
     DevBuf d_tri_dbg;                            // development builds: the triangle kernel's per-workgroup timeline
-    // Ray queries (rt_trace_rays_host / rt_pick): their own stream, staging buffers that grow as needed, and the event behind the
+    // Ray queries (rt_trace_rays_host / rt_pick): query_stream, staging buffers that grow as needed, and ev_query behind the
     // latest query on any stream -- scene writes wait for it as they wait for the frames in flight (rt_drain)
-    hipStream_t query_stream = nullptr;
     DevBuf d_qrays, d_qhits, d_qxy;
-    hipEvent_t ev_query = nullptr;
     bool query_pending = false;
     bool query_versions = false;         // ... and that query (or one before it since the last drain) read a version of the per-frame buffers
     hipStream_t query_last = nullptr;    // the stream of that query
