@@ -733,7 +733,17 @@ static void sky_flags(const rt_ctx* c, uint32_t& flat, uint32_t& seamless) {
     }
 }
 
-int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
+// ---- a frame (rt_enqueue): its preconditions, its plan, what may drain before it takes a slot of the event ring, its steps ----
+
+// Which of the streams rt_render / rt_render_gather rotate over `s` is; -1: a stream of the caller's (rt_render_to)
+static int own_stream_index(const rt_ctx* c, hipStream_t s) {
+    for (int k = 0; k < kStreams; ++k)
+        if (s == c->streams[k]) return k;
+    return -1;
+}
+
+// The state a frame needs; a triangle scene without a texture gets the default one here.
+static int frame_preconditions(rt_ctx* c) {
     if (!c->W || !c->H) return fail(RT_ERR_STATE, "rt_render: rt_resize has not been called");
     if (!c->have_params) return fail(RT_ERR_STATE, "rt_render: rt_write_params has not been called");
     const bool tri = c->scene_kind == 1;
@@ -753,168 +763,191 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     }
     for (int i = 0; i < 6; ++i)
         if (!c->d_face[i].p) return fail(RT_ERR_STATE, "rt_render: all six cube map faces must be written first");
-    RT_HIP(hipSetDevice(c->device));
+    return RT_OK;
+}
 
-    // ---- which kernels render this frame ----
-    bool filter_ok = false;
-    uint32_t signed_filter = 0;
-    rt_plan(c->scene_bound, c->scene_min_radius, c->params, filter_ok, signed_filter);
+// Which kernels render the frame and what they need first.  Made from the context as the caller left it: frame_plan writes nothing
+// and calls no HIP, and rt_enqueue makes it BEFORE anything that may drain the frames in flight -- a drain is an rt_wait, which
+// changes pipelined_hint and in_flight --, so that a frame is planned the same whether or not it had to wait for a resource.
+struct FramePlan {
+    bool tri, filter_ok;                       // a triangle scene (else spheres); rt_plan: within the filter's range (else the literal kernel)
+    uint32_t signed_filter;
+    int own;                                   // own_stream_index of the frame's stream
+    bool hint;                                 // ... one of the library's, and the caller keeps frames in flight (rt_wait: pipelined_hint)
+    bool use_bvh, queue_pipeline;              // the hierarchy kernel (rt_bvh.hip); the two-kernel brute-force pipeline
+    bool need_prep, need_bvh, refit;           // prep_spheres / the hierarchy first; ... by a refit of the device topology, not a host build
+    uint32_t sky_flat, sky_seamless;
+    bool resolve_pass;                         // rt_bvh.hip: sky_resolve
+    RtLaunchCfg cfg;
+};
+static FramePlan frame_plan(const rt_ctx* c, hipStream_t s) {
+    FramePlan p;
+    p.tri = c->scene_kind == 1;
+    p.filter_ok = false;
+    p.signed_filter = 0;
+    rt_plan(c->scene_bound, c->scene_min_radius, c->params, p.filter_ok, p.signed_filter);
     // Fast mode renders through the bounding-sphere hierarchy (rt_bvh.hip) from 128 spheres on (default,
     // variant 0) -- from 72 on for a caller that keeps frames in flight, where the hierarchy kernel's
     // end-of-frame tail is hidden: at 3840x2160 / 8 bounces the two forms cross at ~110 spheres one frame at a
     // time and at ~60 in flight (96 spheres: 1.33 vs 1.00 ms and 0.76 vs 0.98 ms; profiles/r02/count_sweep.log) --
     // or whenever variant 4 asks for it; variant 5 is the brute-force default, 1-3 its forms.
-    bool own_stream = false;                       // one of the streams rt_render / rt_render_gather rotate over
-    for (int k = 0; k < kStreams; ++k) own_stream = own_stream || s == c->streams[k];
-    const bool hint = own_stream && c->pipelined_hint;
-    const uint32_t bvh_from = hint ? 72u : 128u;
-    const bool use_bvh = !tri && c->mode == RT_MODE_FAST && filter_ok && c->n > 0 &&
-                         (c->variant == 4 || (c->variant == 0 && c->n >= bvh_from));
+    p.own = own_stream_index(c, s);
+    p.hint = p.own >= 0 && c->pipelined_hint;
+    const uint32_t bvh_from = p.hint ? 72u : 128u;
+    p.use_bvh = !p.tri && c->mode == RT_MODE_FAST && p.filter_ok && c->n > 0 &&
+                (c->variant == 4 || (c->variant == 0 && c->n >= bvh_from));
     // Frames in flight: the hierarchy kernel and the triangle kernels write nothing but their
     // own control block and `dst`, so consecutive frames may overlap on the device (the next
     // frame's workgroups start while the last paths of this one finish), and so may the
     // single-kernel brute-force and literal forms; the two-kernel brute-force pipeline shares one
     // path queue and is serialised behind the frames in flight.
-    // (rt_kernels.hip: launch_fast -- variants 2 and 3 force the pipeline, 0 / 5 take it from 320 spheres on)
-    const bool queue_pipeline = !tri && !use_bvh && c->mode == RT_MODE_FAST && filter_ok &&
-                                (c->variant == 2 || c->variant == 3 ||
-                                 ((c->variant == 0 || c->variant == 4 || c->variant == 5) && c->n >= 320u));
-    const bool overlap_ok = !queue_pipeline;
-    const bool need_prep = !tri && c->n && (!c->prep_spheres_valid || (!use_bvh && !c->prep_params_valid));
-    const bool need_bvh = use_bvh && !c->bvh_valid;
+    p.cfg.mode = p.filter_ok ? c->mode : (int)RT_MODE_STRICT;
+    p.cfg.variant = (c->variant == 4 || c->variant == 5) ? 0 : c->variant;   // rt_kernels.hip numbers its default 0
+    p.queue_pipeline = !p.tri && !p.use_bvh && c->mode == RT_MODE_FAST && p.filter_ok && rt_trace_wants_queue(c->n, p.cfg);
+    p.need_prep = !p.tri && c->n && (!c->prep_spheres_valid || (!p.use_bvh && !c->prep_params_valid));
+    p.need_bvh = p.use_bvh && !c->bvh_valid;
+    p.refit = p.need_bvh && c->bvh_topo_n == c->n && c->bvh_topo_n != 0u;
+    sky_flags(c, p.sky_flat, p.sky_seamless);
+    p.resolve_pass = p.use_bvh && !p.sky_flat;
+    return p;
+}
 
-    RtLaunchCfg cfg;
-    cfg.mode = filter_ok ? c->mode : (int)RT_MODE_STRICT;
-    cfg.variant = (c->variant == 4 || c->variant == 5) ? 0 : c->variant;   // rt_kernels.hip numbers its default 0
-    // A brute-force variant none of whose forms holds the scene (1 above 2,176 spheres, 2 and 3 above 3,264, up to the
-    // 4,608 from which every variant reads the records from global memory) is refused here: before anything of the frame
-    // is enqueued, a slot of the event ring is taken or the stats change.
-    if (!tri && !use_bvh && !rt_trace_fits(c->n, c->n16, cfg, queue_pipeline)) {
-        char buf[200];
-        std::snprintf(buf, sizeof buf, "rt_render: kernel variant %d has no form for %u spheres (its sphere records exceed the "
-                      "160 KiB of LDS); variant 0 renders any count", c->variant, c->n);
-        return fail(RT_ERR_UNSUPPORTED, buf);
-    }
-    if (queue_pipeline) { int rc = ensure_queue(c); if (rc != RT_OK) return rc; }
-    uint32_t sky_flat, sky_seamless;
-    sky_flags(c, sky_flat, sky_seamless);
-    const bool resolve_pass = use_bvh && !sky_flat;      // rt_bvh.hip: sky_resolve
-    if (resolve_pass) { int rc = ensure_fin(c); if (rc != RT_OK) return rc; }
-    // The hierarchy after rt_write_spheres.  A changed sphere count (or the first frame): host build, here and
-    // now.  The same count: the topology on the device stays, its node bounds are refitted there (below);
-    // a topology the worker thread has finished meanwhile is taken first.  Either way the device arrays may be
-    // rewritten or reallocated: nothing may be in flight (rt_write_spheres has drained already).
-    const bool refit = need_bvh && c->bvh_topo_n == c->n && c->bvh_topo_n != 0u;
-    bool upload_topology = false;
-    if (need_bvh) {
-        int rc = drain(c);
-        if (rc != RT_OK) return rc;
-        uint32_t nodes = c->bvh_nodes;
-        if (!refit) {
-            nodes = rt_bvh_build(c->h_records.data(), c->n, c->h_bvh_rec, c->h_bvh_link, rt_bvh_arity());
+// A brute-force variant none of whose forms holds the scene (1 above 2,176 spheres, 2 and 3 above 3,264, up to the
+// 4,608 from which every variant reads the records from global memory) is refused here: before anything of the frame
+// is enqueued, a slot of the event ring is taken or the stats change.
+static int frame_refused(const rt_ctx* c, const FramePlan& p) {
+    if (p.tri || p.use_bvh || rt_trace_fits(c->n, c->n16, p.cfg, p.queue_pipeline)) return RT_OK;
+    char buf[200];
+    std::snprintf(buf, sizeof buf, "rt_render: kernel variant %d has no form for %u spheres (its sphere records exceed the "
+                  "160 KiB of LDS); variant 0 renders any count", c->variant, c->n);
+    return fail(RT_ERR_UNSUPPORTED, buf);
+}
+
+// The hierarchy after rt_write_spheres, its host side.  A changed sphere count (or the first frame): host build, here and
+// now.  The same count: the topology on the device stays, its node bounds are refitted there (frame_scene_update);
+// a topology the worker thread has finished meanwhile is taken first.  Either way the device arrays may be
+// rewritten or reallocated: nothing may be in flight (rt_write_spheres has drained already).
+static int ensure_hierarchy(rt_ctx* c, const FramePlan& p, bool& upload_topology) {
+    upload_topology = false;
+    if (!p.need_bvh) return RT_OK;
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    uint32_t nodes = c->bvh_nodes;
+    if (!p.refit) {
+        nodes = rt_bvh_build(c->h_records.data(), c->n, c->h_bvh_rec, c->h_bvh_link, rt_bvh_arity());
+        upload_topology = true;
+    } else if (c->rebuild) {
+        std::lock_guard<std::mutex> lk(c->rebuild->m);
+        if (c->rebuild->ready && c->rebuild->out_n == c->n) {
+            c->h_bvh_rec.swap(c->rebuild->out_rec);
+            c->h_bvh_link.swap(c->rebuild->out_link);
+            nodes = c->rebuild->out_nodes;
             upload_topology = true;
-        } else if (c->rebuild) {
-            std::lock_guard<std::mutex> lk(c->rebuild->m);
-            if (c->rebuild->ready && c->rebuild->out_n == c->n) {
-                c->h_bvh_rec.swap(c->rebuild->out_rec);
-                c->h_bvh_link.swap(c->rebuild->out_link);
-                nodes = c->rebuild->out_nodes;
-                upload_topology = true;
-            }
-            c->rebuild->ready = false;
         }
-        if (((size_t)nodes + 1u) * sizeof(uint32_t) > c->d_bvh_link.cap) {      // the second of the pair: both hold as many nodes
-            c->d_bvh_rec.reset(); c->d_bvh_link.reset();
-            RT_HIP(c->d_bvh_rec.replace(((size_t)nodes + 1u) * sizeof(float4)));
-            RT_HIP(c->d_bvh_link.replace(((size_t)nodes + 1u) * sizeof(uint32_t)));
-        }
-        c->bvh_nodes = nodes;
+        c->rebuild->ready = false;
     }
-    // ---- what the triangle kernels read beside the reference's buffers: built here, BEFORE a slot of the event ring is
-    // taken (both may have to drain the frames in flight, which empties the ring) ----
-    if (tri) { int rc = ensure_corners(c, s); if (rc != RT_OK) return rc; }
-    // The relinked pair records of the BLAS trees (rt_flow_build.h), for scenes whose instance data travels with the frame (up
-    // to 16 instances) and whose indices fit 16 bits: rebuilt when a write has reached the nodes the copy was made from or a
-    // frame names a root it does not know -- from the union of the roots it knows and the new ones, so that a host that
-    // alternates root sets between frames pays for each root once.
-    uint32_t root_meta[kInstMax] = {0};
-    bool have_pairs = false;       // the relinked copy is current and covers this frame's roots
-    if (tri && c->kernel != RT_KERNEL_HEATMAP && c->variant != 6) {
-        const uint32_t n_nodes = (uint32_t)(c->nodes_used / 32u);
-        uint32_t roots[kInstMax], n_inst = 0;
-        if (tri_pair_roots(c, roots, n_inst)) {
-            // (the per-frame head of the node buffer lives in inst.head until a frame carries it: the mirror has it already)
-            const bool stale = c->flow_dirty || c->flow.n_nodes != n_nodes;
-            const bool need = stale || !rt_flow_covers(c->flow, roots, n_inst);
-            ++c->flow_frames_since;
-            // A host that invalidates the copy with every frame (it rewrites BLAS nodes per frame: nothing says it may not) would
-            // pay a drain, a host-side rebuild of every tree and an upload per frame for records that live one frame.  Four frames
-            // in a row that each had to rebuild: the node walk (which reads the reference's buffer as written) for the next sixty,
-            // then another try.
-            if (need && c->flow_cooldown > 0u) {
-                --c->flow_cooldown;
-            } else if (need) {
-                c->flow_streak = c->flow_frames_since <= 1u ? c->flow_streak + 1u : 1u;
-                c->flow_frames_since = 0u;
-                if (c->flow_streak >= 4u) { c->flow_cooldown = 60u; c->flow_streak = 0u; }
-                { int rc = drain(c); if (rc != RT_OK) return rc; }
-                std::vector<uint32_t> all(roots, roots + n_inst);
-                if (!stale) all.insert(all.end(), c->flow.roots.begin(), c->flow.roots.end());   // roots already known stay known
-                rt_flow_build(c->h_nodes.data(), n_nodes, all.data(), (uint32_t)all.size(), c->flow);
-                c->flow_dirty = false;
-                ++c->flow_gen;
-                ++c->stats.pair_rebuilds;
-                if (c->flow.ok && c->flow.n_pairs) {
-                    int rc = write_buf(c, c->d_flow, 0, c->flow.pairs.data(), (size_t)c->flow.n_pairs * 64u, "flow pairs");
-                    if (rc != RT_OK) return rc;
-                }
-            }
-            have_pairs = tri_pairs_current(c, roots, n_inst, root_meta);
-        }
+    if (((size_t)nodes + 1u) * sizeof(uint32_t) > c->d_bvh_link.cap) {      // the second of the pair: both hold as many nodes
+        c->d_bvh_rec.reset(); c->d_bvh_link.reset();
+        RT_HIP(c->d_bvh_rec.replace(((size_t)nodes + 1u) * sizeof(float4)));
+        RT_HIP(c->d_bvh_link.replace(((size_t)nodes + 1u) * sizeof(uint32_t)));
     }
-    if (c->in_flight == RT355_MAX_IN_FLIGHT) {   // event ring full: drain
-        int rc = rt_wait(c);
-        if (rc != RT_OK) return rc;
-    }
-    const uint32_t slot = c->in_flight;
+    c->bvh_nodes = nodes;
+    return RT_OK;
+}
 
-    // ---- ordering against the frames in flight and against the last scene update ----
-    if (need_prep || need_bvh || !overlap_ok) {
+// The relinked pair records of the BLAS trees (rt_flow_build.h), for scenes whose instance data travels with the frame (up
+// to 16 instances) and whose indices fit 16 bits: rebuilt when a write has reached the nodes the copy was made from or a
+// frame names a root it does not know -- from the union of the roots it knows and the new ones, so that a host that
+// alternates root sets between frames pays for each root once.  have_pairs: the copy is current and covers this frame's roots.
+// (The counters move in a frame that fails later, too.)
+static int ensure_pairs(rt_ctx* c, uint32_t (&root_meta)[kInstMax], bool& have_pairs) {
+    have_pairs = false;
+    if (c->kernel == RT_KERNEL_HEATMAP || c->variant == 6) return RT_OK;
+    const uint32_t n_nodes = (uint32_t)(c->nodes_used / 32u);
+    uint32_t roots[kInstMax], n_inst = 0;
+    if (!tri_pair_roots(c, roots, n_inst)) return RT_OK;
+    // (the per-frame head of the node buffer lives in inst.head until a frame carries it: the mirror has it already)
+    const bool stale = c->flow_dirty || c->flow.n_nodes != n_nodes;
+    const bool need = stale || !rt_flow_covers(c->flow, roots, n_inst);
+    ++c->flow_frames_since;
+    // A host that invalidates the copy with every frame (it rewrites BLAS nodes per frame: nothing says it may not) would
+    // pay a drain, a host-side rebuild of every tree and an upload per frame for records that live one frame.  Four frames
+    // in a row that each had to rebuild: the node walk (which reads the reference's buffer as written) for the next sixty,
+    // then another try.
+    if (need && c->flow_cooldown > 0u) {
+        --c->flow_cooldown;
+    } else if (need) {
+        c->flow_streak = c->flow_frames_since <= 1u ? c->flow_streak + 1u : 1u;
+        c->flow_frames_since = 0u;
+        if (c->flow_streak >= 4u) { c->flow_cooldown = 60u; c->flow_streak = 0u; }
+        { int rc = drain(c); if (rc != RT_OK) return rc; }
+        std::vector<uint32_t> all(roots, roots + n_inst);
+        if (!stale) all.insert(all.end(), c->flow.roots.begin(), c->flow.roots.end());   // roots already known stay known
+        rt_flow_build(c->h_nodes.data(), n_nodes, all.data(), (uint32_t)all.size(), c->flow);
+        c->flow_dirty = false;
+        ++c->flow_gen;
+        ++c->stats.pair_rebuilds;
+        if (c->flow.ok && c->flow.n_pairs) {
+            int rc = write_buf(c, c->d_flow, 0, c->flow.pairs.data(), (size_t)c->flow.n_pairs * 64u, "flow pairs");
+            if (rc != RT_OK) return rc;
+        }
+    }
+    have_pairs = tri_pairs_current(c, roots, n_inst, root_meta);
+    return RT_OK;
+}
+
+// Everything of a frame that may drain the frames in flight -- which empties the event ring --, and so all of it BEFORE the frame
+// takes its slot: the refusal, the lazily made buffers, the hierarchy's host side, and what the triangle kernels read beside the
+// reference's buffers (the corner array, the pair records).  No other step of a frame calls drain.
+static int frame_resources(rt_ctx* c, const FramePlan& p, hipStream_t s, bool& upload_topology, uint32_t (&root_meta)[kInstMax], bool& have_pairs) {
+    { int rc = frame_refused(c, p); if (rc != RT_OK) return rc; }
+    if (p.queue_pipeline) { int rc = ensure_queue(c); if (rc != RT_OK) return rc; }
+    if (p.resolve_pass) { int rc = ensure_fin(c); if (rc != RT_OK) return rc; }
+    { int rc = ensure_hierarchy(c, p, upload_topology); if (rc != RT_OK) return rc; }
+    have_pairs = false;
+    if (p.tri) {
+        { int rc = ensure_corners(c, s); if (rc != RT_OK) return rc; }
+        { int rc = ensure_pairs(c, root_meta, have_pairs); if (rc != RT_OK) return rc; }
+    }
+    if (c->in_flight == RT355_MAX_IN_FLIGHT) return rt_wait(c);   // event ring full
+    return RT_OK;
+}
+
+extern "C++" {
+// The sphere arrays in d_scene (rt_ctx.h: eight float4 arrays of n16), with the parameters and the counts, as the frame kernels
+// read them (RtFrameArgs) and as prep_spheres writes them (RtPrepArgs)
+template <typename ARGS>
+static void sphere_arrays(const rt_ctx* c, ARGS& a) {
+    std::memcpy(a.p, c->params, sizeof a.p);
+    a.N = c->n; a.N16 = c->n16;
+    float4* b = c->d_scene.as<float4>();
+    const uint32_t m = c->n16;
+    a.geo = b; a.lgt = b + m; a.cam = b + 2u * m; a.col = b + 3u * m;
+    a.geo_f = b + 4u * m; a.lgt_f = b + 5u * m; a.cam_f = b + 6u * m;
+    float* w = reinterpret_cast<float*>(b + 7u * m);
+    a.geo_w = w; a.lgt_w = w + m; a.cam_w = w + 2u * m;
+}
+}
+
+// Ordering against the frames in flight and against the last scene update
+static int frame_order(rt_ctx* c, const FramePlan& p, hipStream_t s) {
+    if (p.need_prep || p.need_bvh || p.queue_pipeline) {
         for (uint32_t i = 0; i < c->in_flight; ++i) RT_HIP(hipStreamWaitEvent(s, c->ev_k1[i], 0));
     }
     if (c->scene_stream && c->scene_stream != s) RT_HIP(hipStreamWaitEvent(s, c->ev_scene, 0));
+    return RT_OK;
+}
 
-    RtFrameArgs fa;
-    std::memcpy(fa.p, c->params, sizeof fa.p);
-    fa.W = c->W; fa.H = c->H; fa.N = c->n; fa.N16 = c->n16;
-    fa.tile_first = c->rank; fa.tile_step = c->world; fa.n_local_tiles = local_tiles(c);
-    fa.signed_filter = signed_filter;
-    {
-        const float4* b = c->d_scene.as<float4>();
-        const uint32_t m = c->n16;
-        fa.geo = b; fa.lgt = b + m; fa.cam = b + 2u * m; fa.col = b + 3u * m;
-        fa.geo_f = b + 4u * m; fa.lgt_f = b + 5u * m; fa.cam_f = b + 6u * m;
-        const float* w = reinterpret_cast<const float*>(b + 7u * m);
-        fa.geo_w = w; fa.lgt_w = w + m; fa.cam_w = w + 2u * m;
-    }
-
-    RT_HIP(hipEventRecord(c->ev_prep0[slot], s));
-    if (need_prep) {
+// What the plan says must run before the frame's kernel: prep_spheres, the hierarchy's upload, refit and fill
+static int frame_scene_update(rt_ctx* c, const FramePlan& p, bool upload_topology, const RtFrameArgs& fa, hipStream_t s) {
+    if (p.need_prep) {
         RtPrepArgs pa;
-        std::memcpy(pa.p, c->params, sizeof pa.p);
-        pa.N = c->n; pa.N16 = c->n16;
+        sphere_arrays(c, pa);
         pa.records = c->d_records.as<float>();
-        float4* b = c->d_scene.as<float4>();
-        const uint32_t m = c->n16;
-        pa.geo = b; pa.lgt = b + m; pa.cam = b + 2u * m; pa.col = b + 3u * m;
-        pa.geo_f = b + 4u * m; pa.lgt_f = b + 5u * m; pa.cam_f = b + 6u * m;
-        float* w = reinterpret_cast<float*>(b + 7u * m);
-        pa.geo_w = w; pa.lgt_w = w + m; pa.cam_w = w + 2u * m;
         RT_HIP(rt_launch_prep(pa, s));
         c->prep_spheres_valid = true;
         c->prep_params_valid = true;
     }
-    if (need_bvh) {
+    if (p.need_bvh) {
         if (upload_topology) {
             const size_t nn = (size_t)c->bvh_nodes + 1u;
             RT_HIP(hipMemcpyAsync(c->d_bvh_rec.p, c->h_bvh_rec.data(), nn * sizeof(float4), hipMemcpyHostToDevice, s));
@@ -923,131 +956,184 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
             c->bvh_topo_n = c->n;
         }
         // bounds of the inner nodes for the current positions (a topology from the worker was built for older ones)
-        if (refit) RT_HIP(rt_launch_bvh_refit(c->d_bvh_rec.as<float4>(), c->d_bvh_link.as<uint32_t>(), c->bvh_nodes, c->d_records.as<float>(), s));
+        if (p.refit) RT_HIP(rt_launch_bvh_refit(c->d_bvh_rec.as<float4>(), c->d_bvh_link.as<uint32_t>(), c->bvh_nodes, c->d_records.as<float>(), s));
         RT_HIP(rt_launch_bvh_fill(c->d_bvh_rec.as<float4>(), c->d_bvh_link.as<uint32_t>(), c->bvh_nodes, fa.geo_f, s));
         c->bvh_valid = true;
     }
-    if (need_prep || need_bvh) {
+    if (p.need_prep || p.need_bvh) {
         RT_HIP(hipEventRecord(c->ev_scene, s));
         c->scene_stream = s;
     }
-    fa.bvh_rec = use_bvh ? c->d_bvh_rec.as<float4>() : nullptr;
-    fa.bvh_link = use_bvh ? c->d_bvh_link.as<uint32_t>() : nullptr;
-    fa.bvh_nodes = use_bvh ? c->bvh_nodes : 0u;
-    // frames in flight on DIFFERENT streams run concurrently and share the chip: this frame's grid is
-    // 1 / (number of distinct streams among it and the kStreams-1 frames enqueued before it)
-    c->slot_stream[slot] = s;
-    fa.grid_share = 1u;
-    if (overlap_ok) {
-        hipStream_t seen[kStreams] = {s};
-        uint32_t distinct = 1;
-        for (uint32_t back = 1; back < (uint32_t)kStreams && back <= slot; ++back) {
-            hipStream_t o = c->slot_stream[slot - back];
-            bool known = false;
-            for (uint32_t j = 0; j < distinct; ++j) known = known || seen[j] == o;
-            if (!known) seen[distinct++] = o;
-        }
-        fa.grid_share = distinct;
-        // a caller that has been enqueuing frames back to back through rt_render / rt_render_gather (the library's
-        // own rotation over kStreams streams) gets equal shares from the first frame of a batch on (rt_bvh.hip:
-        // launch_bvh_as); one that waits after every frame keeps the whole chip, and frames a host enqueues on its
-        // own stream(s) through rt_render_to share the chip by the streams actually in use, whatever the history
-        if (hint) fa.grid_share = (uint32_t)kStreams;
-    }
+    return RT_OK;
+}
 
+// frames in flight on DIFFERENT streams run concurrently and share the chip: this frame's grid is
+// 1 / (number of distinct streams among it and the kStreams-1 frames enqueued before it); reads slot_stream[slot]
+static uint32_t frame_grid_share(const rt_ctx* c, const FramePlan& p, uint32_t slot) {
+    if (p.queue_pipeline) return 1u;
+    // a caller that has been enqueuing frames back to back through rt_render / rt_render_gather (the library's
+    // own rotation over kStreams streams) gets equal shares from the first frame of a batch on (rt_bvh.hip:
+    // launch_bvh_as); one that waits after every frame keeps the whole chip, and frames a host enqueues on its
+    // own stream(s) through rt_render_to share the chip by the streams actually in use, whatever the history
+    if (p.hint) return (uint32_t)kStreams;
+    hipStream_t seen[kStreams] = {c->slot_stream[slot]};
+    uint32_t distinct = 1;
+    for (uint32_t back = 1; back < (uint32_t)kStreams && back <= slot; ++back) {
+        hipStream_t o = c->slot_stream[slot - back];
+        bool known = false;
+        for (uint32_t j = 0; j < distinct; ++j) known = known || seen[j] == o;
+        if (!known) seen[distinct++] = o;
+    }
+    return distinct;
+}
+
+// The frame's arguments but grid_share: no HIP call
+static void frame_args(const rt_ctx* c, const FramePlan& p, uint32_t slot, uint8_t* dst, RtFrameArgs& fa) {
+    sphere_arrays(c, fa);
+    fa.W = c->W; fa.H = c->H;
+    fa.tile_first = c->rank; fa.tile_step = c->world; fa.n_local_tiles = local_tiles(c);
+    fa.signed_filter = p.signed_filter;
+    fa.bvh_rec = p.use_bvh ? c->d_bvh_rec.as<float4>() : nullptr;
+    fa.bvh_link = p.use_bvh ? c->d_bvh_link.as<uint32_t>() : nullptr;
+    fa.bvh_nodes = p.use_bvh ? c->bvh_nodes : 0u;
     // this frame's partial ray counters and its 32-byte control block: one of RT355_MAX_IN_FLIGHT
     // sets, all zeroed by rt_create and again by every frame's epilogue kernel (no memset or read-back by the host)
     unsigned long long* counters = c->d_rays.as<unsigned long long>() + (kCtrlBytes / 8u) * slot;
     unsigned long long* ctrl = counters + kCounterBytes / 8u;
     for (int i = 0; i < 6; ++i) { fa.face[i] = c->d_face[i].as<uint8_t>(); fa.fw[i] = c->fw[i]; fa.fh[i] = c->fh[i]; }
-    fa.sky_flat = sky_flat;
-    fa.sky_seamless = sky_seamless;
+    fa.sky_flat = p.sky_flat;
+    fa.sky_seamless = p.sky_seamless;
     fa.out = dst;
-    // one record buffer per frame that may be running: the frame kStreams slots back must be through with this one
-    fa.fin = resolve_pass ? c->d_fin[slot % (uint32_t)kStreams].as<float4>() : nullptr;
-    if (resolve_pass && slot >= (uint32_t)kStreams) RT_HIP(hipStreamWaitEvent(s, c->ev_k1[slot - (uint32_t)kStreams], 0));
+    // one record buffer per frame that may be running (rt_enqueue waits for the frame kStreams slots back)
+    fa.fin = p.resolve_pass ? c->d_fin[slot % (uint32_t)kStreams].as<float4>() : nullptr;
     fa.rays = counters;
-    fa.queue = queue_pipeline ? c->d_queue.as<float4>() : nullptr;   // rt_kernels.hip takes the pipeline only with a queue
+    fa.queue = p.queue_pipeline ? c->d_queue.as<float4>() : nullptr;   // rt_kernels.hip takes the pipeline only with a queue
     fa.qctrl = reinterpret_cast<uint32_t*>(ctrl) + 2;
-    fa.queue_cap = queue_pipeline ? (uint32_t)c->queue_cap : 0u;
+    fa.queue_cap = p.queue_pipeline ? (uint32_t)c->queue_cap : 0u;
+}
+
+// The triangle scene of the frame in `slot`, the form of the kernel, and the instance data the form reads.
+// Per-frame instance data (RR:169-192) travels with the frame: version `v` of the three buffers is brought to the
+// host's current state by a one-workgroup kernel whose kernarg block holds the values, in front of the ray-trace
+// kernel on the frame's stream.  The frame kVersions slots back read the same version: it must be through.
+// Ordering does not lean on which stream a slot happens to use (a host may rotate rt_render_to over any number of its own
+// streams): before a version is rewritten, EVERY frame in flight that reads it must be through; and a frame that reads a
+// version another stream brought up to date waits for that update.
+// (The small forms of the triangle kernel -- the reference's scene, any scene of a few instances -- read none of the three
+// buffers: their instance data is in the kernel's own arguments, ts.inst.  No kernel, no event, no wait; the versions
+// simply fall behind, and a later frame of another form brings its own up to date.)
+static int frame_tri_scene(rt_ctx* c, const FramePlan& p, uint32_t slot, hipStream_t s, bool have_pairs, const uint32_t (&root_meta)[kInstMax], RtTriScene& ts) {
     const uint32_t v = slot % (uint32_t)kVersions;
-    RtTriScene ts;
-    std::memset(&ts, 0, sizeof ts);
-    if (tri) {
-        tri_scene(c, v, have_pairs, root_meta, ts);
-        ts.tile_order = nullptr; ts.tile_cost = nullptr; ts.xcd_rows = 0u; ts.prio = 0u; ts.in_flight = hint ? 1u : 0u; ts.dbg = nullptr;
-        // which form of the kernel renders the frame (rt_triangles.hip); the small forms take the frame's instance data in their
-        // own arguments, in the layout they stage it in
-        ts.form = (uint32_t)rt_tri_stack_form(ts, c->kernel == RT_KERNEL_HEATMAP);
-        if (ts.form != 0u) {
-            tri_fill_inst(c, ts);
-            if (c->inst_gen_carried != c->inst.gen) { c->inst_gen_carried = c->inst.gen; ++c->stats.instance_uploads; }
-        }
-    }
-    // Per-frame instance data (RR:169-192) travels with the frame: version `v` of the three buffers is brought to the
-    // host's current state by a one-workgroup kernel whose kernarg block holds the values, in front of the ray-trace
-    // kernel on the frame's stream.  The frame kVersions slots back read the same version: it must be through.
-    // Ordering does not lean on which stream a slot happens to use (a host may rotate rt_render_to over any number of its own
-    // streams): before a version is rewritten, EVERY frame in flight that reads it must be through; and a frame that reads a
-    // version another stream brought up to date waits for that update.
-    // (The small forms of the triangle kernel -- the reference's scene, any scene of a few instances -- read none of the three
-    // buffers: their instance data is in the kernel's own arguments, ts.inst above.  No kernel, no event, no wait; the versions
-    // simply fall behind, and a later frame of another form brings its own up to date.)
-    if (tri && ts.form == 0u && c->ver_gen[v] != c->inst.gen) {
+    tri_scene(c, v, have_pairs, root_meta, ts);
+    ts.tile_order = nullptr; ts.tile_cost = nullptr; ts.xcd_rows = 0u; ts.prio = 0u; ts.in_flight = p.hint ? 1u : 0u; ts.dbg = nullptr;
+    // which form of the kernel renders the frame (rt_triangles.hip); the small forms take the frame's instance data in their
+    // own arguments, in the layout they stage it in
+    ts.form = (uint32_t)rt_tri_stack_form(ts, c->kernel == RT_KERNEL_HEATMAP);
+    if (ts.form != 0u) {
+        tri_fill_inst(c, ts);
+        if (c->inst_gen_carried != c->inst.gen) { c->inst_gen_carried = c->inst.gen; ++c->stats.instance_uploads; }
+    } else if (c->ver_gen[v] != c->inst.gen) {
         { int rc = apply_version(c, v, slot, s); if (rc != RT_OK) return rc; }
         ++c->stats.instance_uploads;
-    } else if (tri && ts.form == 0u && c->ev_ver[v] && c->ver_stream[v] != s) {
+    } else if (c->ev_ver[v] && c->ver_stream[v] != s) {
         RT_HIP(hipStreamWaitEvent(s, c->ev_ver[v], 0));
     }
-    // tile order of the triangle kernel: only for frames on the library's own streams (each has its set of buffers)
+    return RT_OK;
+}
+
+// Tile order of the triangle kernel, before the launch: which of the library's sets of buffers the frame uses (-1: none), sized
+// for its order_n tiles.  Only for frames on the library's own streams (each has its set of buffers) ... and only for a caller
+// that waits after each frame (the reference's loop): with frames in flight the tiles of the next frame fill the slots a long
+// tile leaves idle anyway, and row-major order keeps neighbours in one L2
+static int order_prepare(rt_ctx* c, const FramePlan& p, uint32_t order_n, hipStream_t s, int& order_set) {
+    order_set = -1;
+    if (!p.tri || c->kernel == RT_KERNEL_HEATMAP || order_n < kOrderMinTiles || p.hint) return RT_OK;
+    order_set = p.own;
+    if (order_set >= 0 && c->d_tile_cost[order_set].cap < (size_t)order_n * 4u) {
+        // only frames on this stream use the set: wait for them, not for the batch (no slot bookkeeping involved)
+        RT_HIP(hipStreamSynchronize(s));
+        const size_t cap = ((size_t)order_n * 4u + 7u) & ~(size_t)7u, scan_bytes = (size_t)rt_order_scan_words() * 4u;
+        for (rt_ctx::DevBuf* b : {&c->d_tile_cost[order_set], &c->d_tile_order[order_set]}) {
+            RT_HIP(b->replace(cap + scan_bytes));                      // the list carries two header words; behind the costs: order_tiles' bins
+            b->cap = cap;                                              // ... which lie behind `cap`
+        }
+        RT_HIP(hipMemsetAsync(c->d_tile_cost[order_set].p, 0, cap + scan_bytes, s));   // tiles leave their times by atomicMax
+        c->order_tiles[order_set] = 0;
+    }
+    return RT_OK;
+}
+
+// The triangle kernel, with the work list of the frame's set where one has been made for this tile count
+static int frame_launch_triangles(rt_ctx* c, const RtFrameArgs& fa, RtTriScene& ts, int order_set, uint32_t order_n, hipStream_t s) {
+#ifdef RT355_DEV_EXPORTS
+    if (getenv("RT355_TRI_TIMELINE")) {
+        const size_t words = 3u * ((size_t)order_n + 3u * 8192u + 15u * 256u + 64u + 8u * ((c->W + 7u) / 8u));
+        if (c->d_tri_dbg.cap < words * 8u) RT_HIP(c->d_tri_dbg.replace(words * 8u));
+        RT_HIP(hipMemsetAsync(c->d_tri_dbg.p, 0, c->d_tri_dbg.cap, s));
+        ts.dbg = static_cast<unsigned long long*>(c->d_tri_dbg.p);
+    }
+    if (order_set >= 0 && getenv("RT355_KEEP_TILE_COST")) RT_HIP(hipMemsetAsync(c->d_tile_cost[order_set].p, 0, (size_t)order_n * 4u, s));
+#endif
+    if (order_set >= 0) {
+        ts.tile_cost = static_cast<uint32_t*>(c->d_tile_cost[order_set].p);
+        if (c->order_tiles[order_set] == order_n) {
+            ts.tile_order = static_cast<const uint32_t*>(c->d_tile_order[order_set].p);
+            // does that list split tiles?  Then the kernel whose parts' idle lanes trace ahead (the word may be a frame old)
+            ts.roles = __atomic_load_n(&c->h_split[order_set], __ATOMIC_RELAXED) != 0ull ? 1u : 0u;
+        }
+#ifdef RT355_DEV_EXPORTS
+        if (getenv("RT355_TRI_NOLIST")) ts.tile_order = nullptr;
+#endif
+    }
+    RT_HIP(rt_launch_triangles(fa, ts, c->kernel == RT_KERNEL_HEATMAP, s));
+    return RT_OK;
+}
+
+// The list of the set's next frame, made from the times this one leaves.  After the frame's event: rt_wait does not wait for it,
+// the stream's next frame does
+static int order_next(rt_ctx* c, int order_set, uint32_t order_n, hipStream_t s) {
+    uint32_t* const cost = static_cast<uint32_t*>(c->d_tile_cost[order_set].p);
+    uint32_t* const scan = reinterpret_cast<uint32_t*>(static_cast<char*>(c->d_tile_cost[order_set].p) + c->d_tile_cost[order_set].cap);
+    uint32_t* const list = static_cast<uint32_t*>(c->d_tile_order[order_set].p);
+    RT_HIP(rt_launch_order_hist(cost, scan, list, order_n, c->wave_slots, nullptr, nullptr, 0u, c->h_split + order_set, s));
+    RT_HIP(rt_launch_order_scatter(cost, scan, list, order_n, s));
+    c->order_tiles[order_set] = order_n;
+    return RT_OK;
+}
+
+int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
+    { int rc = frame_preconditions(c); if (rc != RT_OK) return rc; }
+    RT_HIP(hipSetDevice(c->device));
+    // the plan first, then everything that may drain: a frame that is refused, or fails, in there has taken no slot
+    const FramePlan p = frame_plan(c, s);
+    bool upload_topology = false, have_pairs = false;
+    uint32_t root_meta[kInstMax] = {0};
+    { int rc = frame_resources(c, p, s, upload_topology, root_meta, have_pairs); if (rc != RT_OK) return rc; }
+
+    // ---- the slot of the event ring, and on the frame's stream: waits, scene update, the frame's own data ----
+    const uint32_t slot = c->in_flight;
+    { int rc = frame_order(c, p, s); if (rc != RT_OK) return rc; }
+    RtFrameArgs fa;
+    frame_args(c, p, slot, dst, fa);
+    RT_HIP(hipEventRecord(c->ev_prep0[slot], s));
+    { int rc = frame_scene_update(c, p, upload_topology, fa, s); if (rc != RT_OK) return rc; }
+    c->slot_stream[slot] = s;
+    fa.grid_share = frame_grid_share(c, p, slot);
+    // the frame kStreams slots back must be through with this frame's end-of-path records (frame_args: fa.fin)
+    if (p.resolve_pass && slot >= (uint32_t)kStreams) RT_HIP(hipStreamWaitEvent(s, c->ev_k1[slot - (uint32_t)kStreams], 0));
+    RtTriScene ts;
+    std::memset(&ts, 0, sizeof ts);
+    if (p.tri) { int rc = frame_tri_scene(c, p, slot, s, have_pairs, root_meta, ts); if (rc != RT_OK) return rc; }
     int order_set = -1;
     const uint32_t order_n = ((c->W + 7u) / 8u) * fa.n_local_tiles;
-    // ... and only for a caller that waits after each frame (the reference's loop): with frames in flight the tiles of
-    // the next frame fill the slots a long tile leaves idle anyway, and row-major order keeps neighbours in one L2
-    if (tri && c->kernel != RT_KERNEL_HEATMAP && order_n >= kOrderMinTiles && !hint) {
-        for (int k = 0; k < kStreams; ++k) if (s == c->streams[k]) order_set = k;
-        if (order_set >= 0 && c->d_tile_cost[order_set].cap < (size_t)order_n * 4u) {
-            // only frames on this stream use the set: wait for them, not for the batch (no slot bookkeeping involved)
-            RT_HIP(hipStreamSynchronize(s));
-            const size_t cap = ((size_t)order_n * 4u + 7u) & ~(size_t)7u, scan_bytes = (size_t)rt_order_scan_words() * 4u;
-            for (rt_ctx::DevBuf* b : {&c->d_tile_cost[order_set], &c->d_tile_order[order_set]}) {
-                RT_HIP(b->replace(cap + scan_bytes));                      // the list carries two header words; behind the costs: order_tiles' bins
-                b->cap = cap;                                              // ... which lie behind `cap`
-            }
-            RT_HIP(hipMemsetAsync(c->d_tile_cost[order_set].p, 0, cap + scan_bytes, s));   // tiles leave their times by atomicMax
-            c->order_tiles[order_set] = 0;
-        }
-    }
+    { int rc = order_prepare(c, p, order_n, s, order_set); if (rc != RT_OK) return rc; }
+
+    // ---- the kernel between its two events, the epilogue, the list of the stream's next frame ----
     RT_HIP(hipEventRecord(c->ev_k0[slot], s));
     g_rt_kernel_id = RT_KID_NONE;
-    if (tri) {
-#ifdef RT355_DEV_EXPORTS
-        if (getenv("RT355_TRI_TIMELINE")) {
-            const size_t words = 3u * ((size_t)order_n + 3u * 8192u + 15u * 256u + 64u + 8u * ((c->W + 7u) / 8u));
-            if (c->d_tri_dbg.cap < words * 8u) RT_HIP(c->d_tri_dbg.replace(words * 8u));
-            RT_HIP(hipMemsetAsync(c->d_tri_dbg.p, 0, c->d_tri_dbg.cap, s));
-            ts.dbg = static_cast<unsigned long long*>(c->d_tri_dbg.p);
-        }
-#endif
-#ifdef RT355_DEV_EXPORTS
-        if (order_set >= 0 && getenv("RT355_KEEP_TILE_COST")) RT_HIP(hipMemsetAsync(c->d_tile_cost[order_set].p, 0, (size_t)order_n * 4u, s));
-#endif
-        if (order_set >= 0) {
-            ts.tile_cost = static_cast<uint32_t*>(c->d_tile_cost[order_set].p);
-            if (c->order_tiles[order_set] == order_n) {
-                ts.tile_order = static_cast<const uint32_t*>(c->d_tile_order[order_set].p);
-                // does that list split tiles?  Then the kernel whose parts' idle lanes trace ahead (the word may be a frame old)
-                ts.roles = __atomic_load_n(&c->h_split[order_set], __ATOMIC_RELAXED) != 0ull ? 1u : 0u;
-            }
-#ifdef RT355_DEV_EXPORTS
-            if (getenv("RT355_TRI_NOLIST")) ts.tile_order = nullptr;
-#endif
-        }
-        RT_HIP(rt_launch_triangles(fa, ts, c->kernel == RT_KERNEL_HEATMAP, s));
-    } else {
-        if (use_bvh) RT_HIP(rt_launch_bvh(fa, s));
-        else RT_HIP(rt_launch_trace(fa, cfg, s));
-    }
+    if (p.tri) { int rc = frame_launch_triangles(c, fa, ts, order_set, order_n, s); if (rc != RT_OK) return rc; }
+    else if (p.use_bvh) RT_HIP(rt_launch_bvh(fa, s));
+    else RT_HIP(rt_launch_trace(fa, p.cfg, s));
     RT_HIP(hipEventRecord(c->ev_k1[slot], s));
 #ifdef RT355_DEV_EXPORTS
     if (order_set >= 0 && getenv("RT355_KEEP_TILE_COST")) {      // tools/tile_cost_probe.py reads the times of whole tiles in index order
@@ -1060,19 +1146,11 @@ int rt_enqueue(rt_ctx* c, uint8_t* dst, hipStream_t s) {
     // that has to wake up first, and its turnaround (15-30 us) is what the work-list kernels behind the event hide in.  (Round 5
     // ran the epilogue inside order_hist's first workgroup to save a link of the chain: the host woke 11 us later and the frame
     // period GREW by as much -- TRI 0.276 -> 0.298 ms; profiles/r05/ref_awaited_trace.log.)
-    RT_HIP(rt_launch_frame_epilogue(counters, c->h_rays.as<unsigned long long>() + 2u * slot, (uint32_t)(kCtrlBytes / 8u), s));
+    RT_HIP(rt_launch_frame_epilogue(fa.rays, c->h_rays.as<unsigned long long>() + 2u * slot, (uint32_t)(kCtrlBytes / 8u), s));
     RT_HIP(hipEventRecord(c->ev_done[slot], s));
-    if (order_set >= 0) {
-        // after the frame's event: rt_wait does not wait for it, the stream's next frame does
-        uint32_t* const cost = static_cast<uint32_t*>(c->d_tile_cost[order_set].p);
-        uint32_t* const scan = reinterpret_cast<uint32_t*>(static_cast<char*>(c->d_tile_cost[order_set].p) + c->d_tile_cost[order_set].cap);
-        uint32_t* const list = static_cast<uint32_t*>(c->d_tile_order[order_set].p);
-        RT_HIP(rt_launch_order_hist(cost, scan, list, order_n, c->wave_slots, nullptr, nullptr, 0u, c->h_split + order_set, s));
-        RT_HIP(rt_launch_order_scatter(cost, scan, list, order_n, s));
-        c->order_tiles[order_set] = order_n;
-    }
+    if (order_set >= 0) { int rc = order_next(c, order_set, order_n, s); if (rc != RT_OK) return rc; }
     c->stats.kernel_id = (uint32_t)g_rt_kernel_id;
-    if (tri) c->stats.tri_form = (uint32_t)g_rt_tri_form;
+    if (p.tri) c->stats.tri_form = (uint32_t)g_rt_tri_form;
     c->stats.grid_share = fa.grid_share;
     c->in_flight = slot + 1;
     return RT_OK;
@@ -1185,13 +1263,10 @@ int rt_wait(rt_ctx* c) {
         // Frames in flight?  Only the library's own rotation counts: a host that enqueues several frames on ONE stream
         // of its own (rt_render_to) has them serialised by that stream, and must not be given a quarter of the chip.
         {
-            uint32_t distinct = 0;
-            for (int k = 0; k < kStreams; ++k) {
-                bool used = false;
-                for (uint32_t i = 0; i < c->in_flight; ++i) used = used || c->slot_stream[i] == c->streams[k];
-                distinct += used ? 1u : 0u;
-            }
-            c->pipelined_hint = distinct > 1u;
+            bool used[kStreams] = {false};
+            for (uint32_t i = 0; i < c->in_flight; ++i)
+                if (const int k = own_stream_index(c, c->slot_stream[i]); k >= 0) used[k] = true;
+            c->pipelined_hint = std::count(used, used + kStreams, true) > 1;
         }
         c->stats.batch_kernel_ms = 0.0f;
         for (uint32_t i = 0; i < c->in_flight; ++i) {

@@ -706,11 +706,12 @@ hipError_t launch_strict(const RtFrameArgs& a, hipStream_t s) {
 // has a path queue.  FastNone: no form of the variant holds the scene -- the host refuses such a frame before it enqueues
 // anything of it (rt_trace_fits).
 enum FastForm { FastNone, FastGlobal, FastSingle, FastPipe8, FastPipe16, FastPipe8Global, FastV2, FastV3 };
+constexpr uint32_t kPipelineFrom = 320u;   // spheres: measured crossover of the two brute-force forms
 
 FastForm fast_form(const RtFrameArgs& a, int variant, bool queue) {
     const size_t rec = (size_t)a.N16 * 16u;
     if (2 * rec + 8u * 8u * 256u > kLdsCap) return FastGlobal;                      // > 4608 spheres: no LDS staging
-    const bool pipeline = queue && a.N >= 320u;   // measured crossover of the two brute-force forms
+    const bool pipeline = queue && a.N >= kPipelineFrom;
     switch (variant) {
         case 0:   // default: two-kernel pipeline for scenes where the sphere loop dominates,
                   // single kernel for small scenes (the queue round trip costs more than it saves)
@@ -778,6 +779,12 @@ bool rt_trace_fits(uint32_t n, uint32_t n16, const RtLaunchCfg& cfg, bool queue)
     std::memset(&a, 0, sizeof a);
     a.N = n; a.N16 = n16;
     return rtk::fast_form(a, cfg.variant, queue) != rtk::FastNone;
+}
+
+// fast_form's other half, for the host: variants 2 and 3 force the pipeline, the default (0) takes it from kPipelineFrom
+// spheres on, variant 1 never does -- and launch_fast takes it only from a frame that brings a queue.
+bool rt_trace_wants_queue(uint32_t n, const RtLaunchCfg& cfg) {
+    return cfg.variant == 2 || cfg.variant == 3 || (cfg.variant == 0 && n >= rtk::kPipelineFrom);
 }
 
 hipError_t rt_launch_prep(const RtPrepArgs& a, hipStream_t s) {

@@ -151,6 +151,9 @@ hipError_t rt_launch_trace(const RtFrameArgs& a, const RtLaunchCfg& cfg, hipStre
 // Does rt_launch_trace have a form for n spheres (n16: n rounded up to 16) under cfg, with or without a path queue?
 // False: the variant's forms cannot hold the scene in LDS, and the launch would fail (rt_kernels.hip: fast_form).
 bool rt_trace_fits(uint32_t n, uint32_t n16, const RtLaunchCfg& cfg, bool queue);
+// Does a fast-mode brute-force frame of n spheres under cfg take the two-kernel pipeline, i.e. must it bring a path queue?
+// (hidden: the library exports what it exported)
+__attribute__((visibility("hidden"))) bool rt_trace_wants_queue(uint32_t n, const RtLaunchCfg& cfg);
 hipError_t rt_launch_bvh(const RtFrameArgs& a, hipStream_t s);
 hipError_t rt_launch_sky_resolve(const RtFrameArgs& a, hipStream_t s);   // textured sky: composes the end-of-path records in a.fin (rt_bvh.hip)
 hipError_t rt_launch_bvh_refit(float4* rec, const uint32_t* link, uint32_t n_nodes, const float* records, hipStream_t s);

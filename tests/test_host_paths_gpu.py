@@ -11,9 +11,10 @@ import pytest
 import compute_raytracer_amd as rt
 from compute_raytracer_amd import abi
 from compute_raytracer_amd.scene_raytracing import CONSTANT_SKY_RGBA
-from helpers import tri_buffers, triangle_scene
+from helpers import leafy_scene, tri_buffers, triangle_scene
 
 pytestmark = pytest.mark.gpu
+MAX_IN_FLIGHT = 64      # include/rt355.h: RT355_MAX_IN_FLIGHT
 
 
 def _renderer(w, h, n, bounces, seed=361):
@@ -155,5 +156,35 @@ def test_streaming_readback_delivers_every_frame_of_a_pipelined_sequence(oracle)
         L = abi.load()
         assert L.rt_read_pixels_async(r._ctx, 4, host[0].ctypes.data, host[0].nbytes) == abi.RT_ERR_INVALID_ARG
         assert L.rt_read_pixels_async(r._ctx, 0, host[0].ctypes.data, 16) == abi.RT_ERR_CAPACITY
+    finally:
+        r.close()
+
+
+@pytest.mark.parametrize("kind", ["spheres", "triangles"])
+def test_a_full_event_ring_waits_inside_and_the_last_frame_is_the_oracles(oracle, kind):
+    """RT355_MAX_IN_FLIGHT + 2 frames without a wait, the camera rewritten before each: the 65th finds the event ring full and
+    waits for the 64 inside rt_render, the last two are the batch that rt_read_pixels completes.  The last frame and its ray
+    count are the oracle's, bit for bit."""
+    sky = rt.CubemapMaterial.constant(CONSTANT_SKY_RGBA)
+    if kind == "spheres":
+        W, H, B = 41, 23, 3
+        scene, mat = rt.synthetic_scene(8, 361), None
+        reference = lambda: oracle.render(scene.pack_params(B), scene.pack_spheres(), sky.faces, W, H)
+    else:
+        W, H, B = 64, 40, 3
+        scene, mat = leafy_scene(2), rt.Material.white()
+        reference = lambda: oracle.render_tri(scene.pack_params(B), tri_buffers(scene, mat), sky.faces, W, H)
+    r = rt.RendererRaytracing(W, H, scene, maxBounces=B).initialize(sky, mat)
+    try:
+        for f in range(MAX_IN_FLIGHT + 2):
+            scene.camera.move(0.01 * ((f % 5) - 2), 0.004)
+            r.recalculateScene()
+            r.enqueue()
+        img = r.read_pixels()
+        ref, _, rays = reference()
+        st = r.stats()
+        assert np.array_equal(img, ref)
+        assert st["rays"] == rays
+        assert st["frames"] == MAX_IN_FLIGHT + 2 and st["batch_frames"] == 2
     finally:
         r.close()
