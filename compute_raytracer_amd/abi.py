@@ -49,6 +49,7 @@ SYMBOLS = [
     "rt_render_ao", "rt_render_ao_host",
     "rt_update_triangles", "rt_refit_blas", "rt_read_nodes", "rt_refit_plan",
     "rt_build_blas", "rt_read_tri_lookup", "rt_build_blas_host",
+    "rt_write_instance_masks", "rt_set_query_masks",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -237,6 +238,8 @@ def load():
         "rt_build_blas": (ctypes.c_int, [vp, ctypes.POINTER(RtBlasRange), u32, ctypes.POINTER(u32)]),
         "rt_read_tri_lookup": (ctypes.c_int, [vp, u32, u32, fp]),
         "rt_build_blas_host": (ctypes.c_int, [fp, u32, fp, u32, fp, u32, ctypes.POINTER(RtBlasRange), u32, ctypes.POINTER(u32)]),
+        "rt_write_instance_masks": (ctypes.c_int, [vp, ctypes.POINTER(u32), u32]),
+        "rt_set_query_masks": (ctypes.c_int, [vp, u32, u32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

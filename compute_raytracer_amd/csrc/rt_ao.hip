@@ -52,14 +52,14 @@ __device__ __forceinline__ void store_ao(const RtAoOut& O, uint32_t x, uint32_t 
 
 // STK / PACKED / PAIRS / P16 / INST as in query_triangles
 template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-__global__ __launch_bounds__(kQueryThreads) void ao_triangles(const RtFrameArgs A, const RtTriScene T, const RtAoOut O) {
+__global__ __launch_bounds__(kQueryThreads) void ao_triangles(const RtFrameArgs A, const RtTriScene T, const RtQueryMask M, const RtAoOut O) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
     __shared__ STK tstacks[kStack * kQueryThreads];
     __shared__ BSTK bstacks[kStack * kQueryThreads];
     __shared__ float4 s_nodes[2 * NODES];
     __shared__ float s_blas[20 * BLAS];
-    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas, &M);
     uint32_t x, y;
     if (!pixel_of_lane(O, x, y)) return;           // (stage_head's barrier was the last one)
     const Scene sc = unpack_scene(A);
@@ -67,16 +67,18 @@ __global__ __launch_bounds__(kQueryThreads) void ao_triangles(const RtFrameArgs 
     RtTriScene Tq = T;                             // (as in query_triangles: a node buffer wholly inside the staged head)
     if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
     float traces = 0.0f;
+    const TriVis vis = {M.table, M.n, M.nearest};      // the primary ray: a nearest-hit search
     const TriHit h = trace_tlas<false, STK, PACKED, PAIRS, P16>(Tq, L, o, d, tstacks + threadIdx.x, bstacks + threadIdx.x,
-                                                                 kQueryThreads, traces);
+                                                                 kQueryThreads, traces, 0.0f, 0.0f, &vis);
     if (h.tri < 0) { store_ao(O, x, y, 0u); return; }
     const uint32_t bi = (uint32_t)h.blas;
     const AoFrame f = ao_frame(o, d, h.t, hit_normal(T, h, bi < L.n_blas ? L.blas + 20u * bi : T.blas + 20u * (size_t)bi));
     uint32_t count = 0u;
+    const TriVis avis = {M.table, M.n, M.occlusion};   // the k rays: rt_occluded's
 #pragma unroll 1
     for (uint32_t j = 0; j < O.k; ++j) {
         const TriHit a = trace_tlas<false, STK, PACKED, PAIRS, P16, kStack, /*LIMITS=*/true, /*ANY=*/true>(
-            Tq, L, f.p, ao_dir(f, O, j), tstacks + threadIdx.x, bstacks + threadIdx.x, kQueryThreads, traces, O.tmin, O.radius);
+            Tq, L, f.p, ao_dir(f, O, j), tstacks + threadIdx.x, bstacks + threadIdx.x, kQueryThreads, traces, O.tmin, O.radius, &avis);
         count += a.tri >= 0 ? 1u : 0u;
     }
     store_ao(O, x, y, count);
@@ -141,8 +143,8 @@ __global__ __launch_bounds__(kQueryThreads) void ao_spheres(const RtFrameArgs A,
 
 }  // namespace rtk
 
-// the three argument blocks of ao_triangles travel by value: together they must fit the 4 KB a kernel's arguments may take
-static_assert(sizeof(RtFrameArgs) + sizeof(RtTriScene) + sizeof(RtAoOut) <= 4096, "ao_triangles' arguments exceed the kernarg segment");
+// the four argument blocks of ao_triangles travel by value: together they must fit the 4 KB a kernel's arguments may take
+static_assert(sizeof(RtFrameArgs) + sizeof(RtTriScene) + sizeof(RtQueryMask) + sizeof(RtAoOut) <= 4096, "ao_triangles' arguments exceed the kernarg segment");
 
 // the rectangle lies in the frame the rays are made for, some plane is asked for, k is in range, and the grid is one the launch can have
 static bool ao_args_ok(const RtFrameArgs& a, const RtAoOut& o) {
@@ -152,10 +154,11 @@ static bool ao_args_ok(const RtFrameArgs& a, const RtAoOut& o) {
 
 // (one form for the primary walk and the k occlusion walks: a ray is walked in the form rt_occluded walks it in)
 hipError_t rt_launch_ao_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtAoOut& o, hipStream_t s) {
+    const RtQueryMask& m = rt_query_mask_of(t);
     if (!ao_args_ok(a, o)) return hipErrorInvalidValue;
     rtk::query_form(t, inst, [&](auto f) {
         typedef decltype(f) F;
-        hipLaunchKernelGGL((rtk::ao_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3((uint32_t)rtk::frame_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, t, o);
+        hipLaunchKernelGGL((rtk::ao_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3((uint32_t)rtk::frame_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, t, m, o);
     });
     return hipGetLastError();
 }

@@ -604,6 +604,41 @@ int rt_set_variant(rt_ctx* c, int variant) {
     return RT_OK;
 }
 
+// ---- instance visibility masks (ray queries alone: no frame reads them) ----
+
+// The table indexes BLAS records and is no part of any scene buffer: it outlives every write of those.  For queries this is a scene
+// write, ordered by ev_query on one side and by completing before it returns on the other: it waits (the host does) for the queries
+// enqueued before it, which keep the table they were enqueued with -- in their arguments, or in the device table this call may only
+// now touch -- and it returns with the device table written, so a query enqueued afterwards, on any stream, reads the new one with no
+// event to wait for.  It copies on the query stream, where no frame runs: no drain, no frame waited for, ev_scene left alone (a frame
+// that waits for ev_scene would otherwise wait here).
+int rt_write_instance_masks(rt_ctx* c, const uint32_t* masks, uint32_t n) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_write_instance_masks: ctx is NULL");
+    if (n && !masks) return fail(RT_ERR_INVALID_ARG, "rt_write_instance_masks: masks is NULL");
+    RT_HIP(hipSetDevice(c->device));
+    if (c->query_pending) RT_HIP(hipEventSynchronize(c->ev_query));   // (not a drain: the frames in flight go on)
+    if (n) {
+        const size_t bytes = (size_t)n * 4u;
+        if (bytes > c->d_masks.cap) RT_HIP(c->d_masks.replace(std::max(bytes, (size_t)256u)));
+        RT_HIP(c->query_stream.ensure(hipStreamNonBlocking));
+        RT_HIP(hipMemcpyAsync(c->d_masks.p, masks, bytes, hipMemcpyHostToDevice, c->query_stream));
+        RT_HIP(hipStreamSynchronize(c->query_stream));
+        c->h_masks.assign(masks, masks + n);
+        c->d_masks.used = bytes;
+    } else {
+        c->h_masks.clear();
+        c->d_masks.used = 0;
+    }
+    return RT_OK;
+}
+
+int rt_set_query_masks(rt_ctx* c, uint32_t nearest, uint32_t occlusion) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_set_query_masks: ctx is NULL");
+    c->mask_nearest = nearest;
+    c->mask_occlusion = occlusion;
+    return RT_OK;
+}
+
 // ---- the triangle scene a kernel reads: one place for frames (rt_enqueue) and ray queries (rt_trace_rays) ----
 
 // The compact corner array follows the triangles and the lookup table: built on `s` by the first frame or query that needs it
@@ -686,8 +721,8 @@ static void tri_scene(const rt_ctx* c, uint32_t v, bool have_pairs, const uint32
 }
 
 // The instance data that travels with a frame (inst.blas_on / lookup_on), by value, in the layout the small forms stage it in
-// (rt_tri_types.h: RtTriInst): the head of the node buffer from the mirror, the records with the lookup entries and the roots'
-// metas (ts.root_meta) in their padding words.
+// (rt_tri_types.h: RtTriInst): the head of the node buffer from the mirror, the records with the lookup entries, the roots' metas
+// (ts.root_meta) and the instances' visibility masks (a ray query reads them; a frame reads none) in their padding words.
 static void tri_fill_inst(const rt_ctx* c, RtTriScene& ts) {
     const uint32_t nn = std::min(ts.n_nodes, kInstHeadNodes), nb = std::min(ts.n_blas, kInstBlas);
     std::memcpy(ts.inst.head, c->h_nodes.data(), (size_t)nn * 32u);
@@ -696,6 +731,8 @@ static void tri_fill_inst(const rt_ctx* c, RtTriScene& ts) {
     for (uint32_t k = 0; k < nb; ++k) {
         if (k < nl) ts.inst.blas[20u * k + 19u] = c->inst.lookup[k];
         std::memcpy(&ts.inst.blas[20u * k + 17u], &ts.root_meta[k], 4);
+        const uint32_t mask = k < c->h_masks.size() ? c->h_masks[k] : 0xFFFFFFFFu;
+        std::memcpy(&ts.inst.blas[20u * k + 18u], &mask, 4);
     }
 }
 
@@ -1841,7 +1878,7 @@ struct Query {
     hipStream_t s;
     bool tri;
     int inst;
-    RtTriScene ts;
+    RtQueryScene ts;     // ... with the instance masks and the context's two ray masks, copied here: at the call
 };
 
 // Opens a query: its stream, and query_prepare on it.  Results in device memory: `hip_stream`, or the context's own when that is
@@ -1854,6 +1891,10 @@ static int query_open(rt_ctx* c, const char* who, bool host, void* hip_stream, Q
     } else {
         q.s = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     }
+    q.ts.mask.table = c->d_masks.as<uint32_t>();
+    q.ts.mask.n = (uint32_t)c->h_masks.size();
+    q.ts.mask.nearest = c->mask_nearest;
+    q.ts.mask.occlusion = c->mask_occlusion;
     return query_prepare(c, who, q.s, q.tri, q.ts, q.inst);
 }
 // Closes it behind the kernels launched on q.s: what the next query on another stream, and rt_drain, wait for

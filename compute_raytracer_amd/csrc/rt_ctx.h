@@ -168,6 +168,13 @@ struct rt_ctx {
     bool query_pending = false;
     bool query_versions = false;         // ... and that query (or one before it since the last drain) read a version of the per-frame buffers
     hipStream_t query_last = nullptr;    // the stream of that query
+    // Instance visibility masks (rt_write_instance_masks, rt_set_query_masks): one 32-bit mask per BLAS record, by record index,
+    // whatever the record count is or becomes; records beyond the table have 0xFFFFFFFF.  The host copy rides in word 18 of the
+    // records a query carries in its arguments (tri_fill_inst); the device copy is what the query kernels read for every other
+    // record.  No frame reads either.
+    std::vector<uint32_t> h_masks;
+    DevBuf d_masks;                      // used: 4 bytes per entry of h_masks
+    uint32_t mask_nearest = 0xFFFFFFFFu, mask_occlusion = 0xFFFFFFFFu;   // the ray masks the next query call copies
     uint32_t n_cus = 256;
     uint32_t tex_w = 0, tex_h = 0;
     int scene_kind = 0;                    // 0 spheres, 1 triangles: the primitive type written last

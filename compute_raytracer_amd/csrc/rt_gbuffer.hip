@@ -35,14 +35,14 @@ __device__ __forceinline__ void store_miss_planes(const RtGbufferOut& O, uint32_
 
 // STK / PACKED / PAIRS / P16 / INST as in query_triangles
 template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-__global__ __launch_bounds__(kQueryThreads) void gbuffer_triangles(const RtFrameArgs A, const RtTriScene T, const RtGbufferOut O) {
+__global__ __launch_bounds__(kQueryThreads) void gbuffer_triangles(const RtFrameArgs A, const RtTriScene T, const RtQueryMask M, const RtGbufferOut O) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
     __shared__ STK tstacks[kStack * kQueryThreads];
     __shared__ BSTK bstacks[kStack * kQueryThreads];
     __shared__ float4 s_nodes[2 * NODES];
     __shared__ float s_blas[20 * BLAS];
-    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas, &M);
     uint32_t x, y;
     if (!pixel_of_lane(O, x, y)) return;           // (stage_head's barrier was the last one)
     const Scene sc = unpack_scene(A);
@@ -50,8 +50,9 @@ __global__ __launch_bounds__(kQueryThreads) void gbuffer_triangles(const RtFrame
     RtTriScene Tq = T;                             // (as in query_triangles: a node buffer wholly inside the staged head)
     if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
     float traces = 0.0f;
+    const TriVis vis = {M.table, M.n, M.nearest};
     const TriHit h = trace_tlas<false, STK, PACKED, PAIRS, P16>(Tq, L, o, d, tstacks + threadIdx.x, bstacks + threadIdx.x,
-                                                                 kQueryThreads, traces);
+                                                                 kQueryThreads, traces, 0.0f, 0.0f, &vis);
     if (h.tri < 0) { store_miss_planes(O, x, y); return; }
     // RK:334-338 for the winner (the staged record keeps the matrix in words 0-15)
     const uint32_t bi = (uint32_t)h.blas;
@@ -94,10 +95,11 @@ static bool gbuffer_args_ok(const RtFrameArgs& a, const RtGbufferOut& o) {
 }
 
 hipError_t rt_launch_gbuffer_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtGbufferOut& o, hipStream_t s) {
+    const RtQueryMask& m = rt_query_mask_of(t);
     if (!gbuffer_args_ok(a, o)) return hipErrorInvalidValue;
     rtk::query_form(t, inst, [&](auto f) {
         typedef decltype(f) F;
-        hipLaunchKernelGGL((rtk::gbuffer_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3((uint32_t)rtk::frame_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, t, o);
+        hipLaunchKernelGGL((rtk::gbuffer_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3((uint32_t)rtk::frame_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, t, m, o);
     });
     return hipGetLastError();
 }

@@ -23,6 +23,11 @@
 // The multi-hit form (rt_trace_rays_multi): the k nearest hits in the order (t, instance, prim), k records per ray.
 //   multi_triangles<K, ...>: multi_tlas (rt_tri_device.h) -- the same walk under the t of the lane's k-th hit, which it keeps with
 //     the others in a sorted register list of capacity K (4 or 8).  multi_spheres<K>: the literal loop into the same list.
+// Instance visibility masks (rt_write_instance_masks, rt_set_query_masks): every triangle kernel here, and those of rt_shade.hip,
+//   rt_sample.hip, rt_gbuffer.hip and rt_ao.hip, takes an RtQueryMask M beside the scene -- the device table of instance masks and
+//   the call's two ray masks.  stage_head puts the masks of the staged records into their word 18; the walks get a TriVis
+//   {table, n, ray mask} and leave an instance whose mask shares no bit with the ray's before its ray transform (rt_tri_device.h).
+//   The sphere kernels take no masks: a sphere scene has no instances.
 #include <type_traits>
 
 #include "rt_device.h"
@@ -44,15 +49,15 @@ __device__ __forceinline__ void store_miss(float4* __restrict__ hits, size_t i) 
 
 // STK / PACKED / PAIRS / P16 as in trace_tlas; INST: the instance data came with the arguments (T.inst, stage_head<..., true>)
 template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-__global__ __launch_bounds__(kQueryThreads) void query_triangles(const RtTriScene T, const float4* __restrict__ rays,
-                                                                 float4* __restrict__ hits, uint32_t n) {
+__global__ __launch_bounds__(kQueryThreads) void query_triangles(const RtTriScene T, const RtQueryMask M,
+                                                                 const float4* __restrict__ rays, float4* __restrict__ hits, uint32_t n) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
     __shared__ STK tstacks[kStack * kQueryThreads];
     __shared__ BSTK bstacks[kStack * kQueryThreads];
     __shared__ float4 s_nodes[2 * NODES];
     __shared__ float s_blas[20 * BLAS];
-    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);   // (INST: roots in T.inst)
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas, &M);   // (INST: roots in T.inst)
     const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
     if (i >= n) return;
     v3 o, d;
@@ -63,8 +68,9 @@ __global__ __launch_bounds__(kQueryThreads) void query_triangles(const RtTriScen
     RtTriScene Tq = T;
     if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
     float traces = 0.0f;
+    const TriVis vis = {M.table, M.n, M.nearest};
     const TriHit h = trace_tlas<false, STK, PACKED, PAIRS, P16>(Tq, L, o, d, tstacks + threadIdx.x, bstacks + threadIdx.x,
-                                                                 kQueryThreads, traces);
+                                                                 kQueryThreads, traces, 0.0f, 0.0f, &vis);
     if (h.tri < 0) { store_miss(hits, i); return; }
     // RK:334-338 for the winner (the staged record keeps the matrix in words 0-15)
     const uint32_t bi = (uint32_t)h.blas;
@@ -121,17 +127,19 @@ __device__ __forceinline__ void load_ray_limits(const float4* __restrict__ rays,
     tmax = limits ? b.w : 9999.0f;
 }
 
-// query_triangles over (tmin, tmax); ANY: rt_occluded (one byte per ray in `occ`), else rt_hit records in `hits`
+// query_triangles over (tmin, tmax); ANY: rt_occluded (one byte per ray in `occ`, the rays carry M.occlusion), else rt_hit records
+// in `hits` (M.nearest)
 template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST, bool ANY>
-__global__ __launch_bounds__(kQueryThreads) void limited_triangles(const RtTriScene T, const float4* __restrict__ rays, uint32_t flags,
-                                                                   float4* __restrict__ hits, uint8_t* __restrict__ occ, uint32_t n) {
+__global__ __launch_bounds__(kQueryThreads) void limited_triangles(const RtTriScene T, const RtQueryMask M, const float4* __restrict__ rays,
+                                                                   uint32_t flags, float4* __restrict__ hits, uint8_t* __restrict__ occ,
+                                                                   uint32_t n) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
     __shared__ STK tstacks[kStack * kQueryThreads];
     __shared__ BSTK bstacks[kStack * kQueryThreads];
     __shared__ float4 s_nodes[2 * NODES];
     __shared__ float s_blas[20 * BLAS];
-    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas, &M);
     const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
     if (i >= n) return;
     v3 o, d;
@@ -140,8 +148,9 @@ __global__ __launch_bounds__(kQueryThreads) void limited_triangles(const RtTriSc
     RtTriScene Tq = T;                             // (as in query_triangles)
     if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
     float traces = 0.0f;
+    const TriVis vis = {M.table, M.n, ANY ? M.occlusion : M.nearest};
     const TriHit h = trace_tlas<false, STK, PACKED, PAIRS, P16, kStack, /*LIMITS=*/true, ANY>(
-        Tq, L, o, d, tstacks + threadIdx.x, bstacks + threadIdx.x, kQueryThreads, traces, tmin, tmax);
+        Tq, L, o, d, tstacks + threadIdx.x, bstacks + threadIdx.x, kQueryThreads, traces, tmin, tmax, &vis);
     if (ANY) { occ[i] = h.tri >= 0 ? 1u : 0u; return; }
     if (h.tri < 0) { store_miss(hits, i); return; }
     const uint32_t bi = (uint32_t)h.blas;
@@ -236,15 +245,15 @@ __global__ __launch_bounds__(kQueryThreads) void occlude_spheres(const float* __
 // multi_tlas, then for each survivor what query_triangles stores for its winner: u and v are formed again by the arithmetic that
 // accepted the triangle (the same operations on the same operands: the same bits), the normal and the triangle index once each
 template <int K, typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-__global__ __launch_bounds__(kQueryThreads) void multi_triangles(const RtTriScene T, const float4* __restrict__ rays, uint32_t flags,
-                                                                 uint32_t k, float4* __restrict__ hits, uint32_t n) {
+__global__ __launch_bounds__(kQueryThreads) void multi_triangles(const RtTriScene T, const RtQueryMask M, const float4* __restrict__ rays,
+                                                                 uint32_t flags, uint32_t k, float4* __restrict__ hits, uint32_t n) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
     __shared__ STK tstacks[kStack * kQueryThreads];
     __shared__ BSTK bstacks[kStack * kQueryThreads];
     __shared__ float4 s_nodes[2 * NODES];
     __shared__ float s_blas[20 * BLAS];
-    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas, &M);
     const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
     if (i >= n) return;
     v3 o, d;
@@ -253,7 +262,8 @@ __global__ __launch_bounds__(kQueryThreads) void multi_triangles(const RtTriScen
     RtTriScene Tq = T;                             // (as in query_triangles)
     if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
     HitList<K, true> list;
-    multi_tlas<K, STK, PACKED, PAIRS, P16>(Tq, L, o, d, list, k, tstacks + threadIdx.x, bstacks + threadIdx.x, kQueryThreads, tmin, tmax);
+    const TriVis vis = {M.table, M.n, M.nearest};
+    multi_tlas<K, STK, PACKED, PAIRS, P16>(Tq, L, o, d, list, k, tstacks + threadIdx.x, bstacks + threadIdx.x, kQueryThreads, tmin, tmax, &vis);
     for (uint32_t j = 0; j < k; ++j) {
         TriHit h;
         int prim;
@@ -333,6 +343,7 @@ __global__ __launch_bounds__(256) void pick_rays(const RtFrameArgs A, const uint
 
 hipError_t rt_launch_multi_triangles(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, uint32_t k, float4* hits,
                                      uint32_t n, hipStream_t s) {
+    const RtQueryMask& m = rt_query_mask_of(t);
     if (n == 0) return hipSuccess;
     if (k == 0 || k > RT355_MAX_HITS) return hipErrorInvalidValue;
     const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
@@ -340,7 +351,7 @@ hipError_t rt_launch_multi_triangles(const RtTriScene& t, int inst, const float4
     const auto launch = [&](auto f, auto cap) {
         typedef decltype(f) F;
         hipLaunchKernelGGL((rtk::multi_triangles<decltype(cap)::value, typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(blocks),
-                           dim3(rtk::kQueryThreads), 0, s, t, rays, flags, k, hits, n);
+                           dim3(rtk::kQueryThreads), 0, s, t, m, rays, flags, k, hits, n);
     };
     if (k <= 4u) rtk::query_form(t, inst, [&](auto f) { launch(f, std::integral_constant<int, 4>()); });
     else         rtk::query_form(t, inst, [&](auto f) { launch(f, std::integral_constant<int, 8>()); });
@@ -358,11 +369,12 @@ hipError_t rt_launch_multi_spheres(const float* records, uint32_t n_spheres, con
 }
 
 hipError_t rt_launch_query_triangles(const RtTriScene& t, int inst, const float4* rays, float4* hits, uint32_t n, hipStream_t s) {
+    const RtQueryMask& m = rt_query_mask_of(t);
     if (n == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
     rtk::query_form(t, inst, [&](auto f) {
         typedef decltype(f) F;
-        hipLaunchKernelGGL((rtk::query_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(blocks), dim3(rtk::kQueryThreads), 0, s, t, rays, hits, n);
+        hipLaunchKernelGGL((rtk::query_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(blocks), dim3(rtk::kQueryThreads), 0, s, t, m, rays, hits, n);
     });
     return hipGetLastError();
 }
@@ -376,6 +388,7 @@ hipError_t rt_launch_query_spheres(const float* records, uint32_t n_spheres, con
 
 hipError_t rt_launch_limited_triangles(const RtTriScene& t, int inst, const float4* rays, uint32_t flags, bool any, void* out,
                                        uint32_t n, hipStream_t s) {
+    const RtQueryMask& m = rt_query_mask_of(t);
     if (n == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
     // ANY is the outer choice, the scene's form the inner one
@@ -383,7 +396,7 @@ hipError_t rt_launch_limited_triangles(const RtTriScene& t, int inst, const floa
         typedef decltype(f) F;
         constexpr bool ANY = decltype(any_form)::value;
         hipLaunchKernelGGL((rtk::limited_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST, ANY>), dim3(blocks), dim3(rtk::kQueryThreads),
-                           0, s, t, rays, flags, ANY ? nullptr : static_cast<float4*>(out), ANY ? static_cast<uint8_t*>(out) : nullptr, n);
+                           0, s, t, m, rays, flags, ANY ? nullptr : static_cast<float4*>(out), ANY ? static_cast<uint8_t*>(out) : nullptr, n);
     };
     if (any) rtk::query_form(t, inst, [&](auto f) { launch(f, std::true_type()); });
     else     rtk::query_form(t, inst, [&](auto f) { launch(f, std::false_type()); });

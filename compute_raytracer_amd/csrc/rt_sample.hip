@@ -50,7 +50,7 @@ __device__ __forceinline__ void resolve_samples(const RtSampleOut& O, const floa
 
 // STK / PACKED / PAIRS / P16 / INST as in shade_triangles
 template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-__global__ __launch_bounds__(kQueryThreads) void sample_triangles(const RtFrameArgs A, const RtTriScene T, const RtSampleOut O) {
+__global__ __launch_bounds__(kQueryThreads) void sample_triangles(const RtFrameArgs A, const RtTriScene T, const RtQueryMask M, const RtSampleOut O) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
     __shared__ STK tstacks[kStack * kQueryThreads];
@@ -58,14 +58,15 @@ __global__ __launch_bounds__(kQueryThreads) void sample_triangles(const RtFrameA
     __shared__ float4 s_nodes[2 * NODES];
     __shared__ float s_blas[20 * BLAS];
     __shared__ float4 s_col[kQueryThreads];
-    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas, &M);
     uint32_t px = 0, py = 0;
     if (sample_of_lane(O, px, py)) {               // (every lane reaches the barrier below)
         RtTriScene Tq = T;                         // (as in query_triangles: a node buffer wholly inside the staged head)
         if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
         const Scene sc = unpack_scene(A);
+        const TriVis vis = {M.table, M.n, M.nearest};
         const PathEnd e = path_triangles<STK, PACKED, PAIRS, P16>(T, Tq, L, sc, sc.cameraPos, primary_dir(A, sc, px, py),
-                                                                  tstacks + threadIdx.x, bstacks + threadIdx.x);
+                                                                  tstacks + threadIdx.x, bstacks + threadIdx.x, vis);
         // (the fog colour: the sky along the primary ray, formed again rather than carried through the bounce loop)
         const v3 color = path_colour(A, sc, e, true, [&]() { return primary_dir(A, sc, px, py); });
         s_col[threadIdx.x] = make_float4(color.x, color.y, color.z, 0.0f);
@@ -111,10 +112,11 @@ static bool sample_args_ok(const RtFrameArgs& a, const RtSampleOut& o) {
 }
 
 hipError_t rt_launch_sample_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtSampleOut& o, hipStream_t s) {
+    const RtQueryMask& m = rt_query_mask_of(t);
     if (!sample_args_ok(a, o)) return hipErrorInvalidValue;
     rtk::query_form(t, inst, [&](auto f) {
         typedef decltype(f) F;
-        hipLaunchKernelGGL((rtk::sample_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(rtk::sample_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, t, o);
+        hipLaunchKernelGGL((rtk::sample_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(rtk::sample_blocks(o)), dim3(rtk::kQueryThreads), 0, s, a, t, m, o);
     });
     return hipGetLastError();
 }

@@ -37,15 +37,16 @@ __device__ __forceinline__ void shade_finish(const RtFrameArgs& A, const Scene& 
 
 // STK / PACKED / PAIRS / P16 / INST as in limited_triangles (rt_query.hip)
 template <typename STK, bool PACKED, bool PAIRS, bool P16, bool INST>
-__global__ __launch_bounds__(kQueryThreads) void shade_triangles(const RtFrameArgs A, const RtTriScene T, const float4* __restrict__ rays,
-                                                                 uint32_t flags, float4* __restrict__ out, uint32_t n) {
+__global__ __launch_bounds__(kQueryThreads) void shade_triangles(const RtFrameArgs A, const RtTriScene T, const RtQueryMask M,
+                                                                 const float4* __restrict__ rays, uint32_t flags, float4* __restrict__ out,
+                                                                 uint32_t n) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     constexpr uint32_t NODES = INST ? kWideNodes : kLdsNodes, BLAS = INST ? kWideBlas : kLdsBlas;
     __shared__ STK tstacks[kStack * kQueryThreads];
     __shared__ BSTK bstacks[kStack * kQueryThreads];
     __shared__ float4 s_nodes[2 * NODES];
     __shared__ float s_blas[20 * BLAS];
-    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas);
+    const TriLds L = stage_head<kQueryWaves, NODES, BLAS, INST, /*ROOTS=*/false>(T, s_nodes, s_blas, &M);
     const size_t i = (size_t)blockIdx.x * kQueryThreads + threadIdx.x;
     if (i >= n) return;                            // (no barrier after the staging)
     v3 ro, rd;
@@ -53,7 +54,8 @@ __global__ __launch_bounds__(kQueryThreads) void shade_triangles(const RtFrameAr
     RtTriScene Tq = T;                             // (as in query_triangles: a node buffer wholly inside the staged head)
     if (INST && T.n_nodes <= L.n_nodes) Tq.nodes = s_nodes;
     const Scene sc = unpack_scene(A);
-    const PathEnd e = path_triangles<STK, PACKED, PAIRS, P16>(T, Tq, L, sc, ro, rd, tstacks + threadIdx.x, bstacks + threadIdx.x);
+    const TriVis vis = {M.table, M.n, M.nearest};
+    const PathEnd e = path_triangles<STK, PACKED, PAIRS, P16>(T, Tq, L, sc, ro, rd, tstacks + threadIdx.x, bstacks + threadIdx.x, vis);
     shade_finish(A, sc, rays, flags, out, i, e);
 }
 
@@ -80,11 +82,12 @@ __global__ __launch_bounds__(kQueryThreads) void shade_spheres(const RtFrameArgs
 
 hipError_t rt_launch_shade_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const float4* rays, uint32_t flags, float4* out,
                                      uint32_t n, hipStream_t s) {
+    const RtQueryMask& m = rt_query_mask_of(t);
     if (n == 0) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((size_t)n + rtk::kQueryThreads - 1u) / rtk::kQueryThreads);
     rtk::query_form(t, inst, [&](auto f) {
         typedef decltype(f) F;
-        hipLaunchKernelGGL((rtk::shade_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(blocks), dim3(rtk::kQueryThreads), 0, s, a, t, rays, flags, out, n);
+        hipLaunchKernelGGL((rtk::shade_triangles<typename F::STK, F::PACKED, F::PAIRS, F::P16, F::INST>), dim3(blocks), dim3(rtk::kQueryThreads), 0, s, a, t, m, rays, flags, out, n);
     });
     return hipGetLastError();
 }

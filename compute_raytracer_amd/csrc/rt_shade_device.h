@@ -40,17 +40,18 @@ __device__ __forceinline__ v3 path_colour(const RtFrameArgs& A, const Scene& sc,
 
 // The bounce loop of trace_triangles (rt_triangles.hip) without tiles, work list, ray counters or parking: per bounce trace_tlas
 // along the path, the hit's normal, albedo and texture sample, the reflection, trace_tlas from the light, the shadow test, the
-// running mean.  Tq: T, or T with the staged node buffer (query_triangles); the stacks are the lane's own, slot-major.
+// running mean.  Tq: T, or T with the staged node buffer (query_triangles); the stacks are the lane's own, slot-major.  vis: what the
+// path rays and the shadow rays alike may see -- RK:147-165 is a nearest-hit search too.
 template <typename STK, bool PACKED, bool PAIRS, bool P16, typename BSTK>
 __device__ __forceinline__ PathEnd path_triangles(const RtTriScene& T, const RtTriScene& Tq, const TriLds& L, const Scene& sc, v3 ro, v3 rd,
-                                                  STK* tstack, BSTK* bstack) {
+                                                  STK* tstack, BSTK* bstack, const TriVis& vis) {
     float dummy = 0.0f;
     v3 color = V(1.0f, 1.0f, 1.0f);                // RK:103
     float dist = 0.0f;                             // RK:102: 0 unless the first ray hits (RK:116-118)
     float affect = 1.0f, sum = 0.0f;               // RK:111-112
     bool missed = false;
     for (uint32_t bounce = 0; bounce < sc.bounces; ++bounce) {                       // RK:113
-        const TriHit h = trace_tlas<false, STK, PACKED, PAIRS, P16>(Tq, L, ro, rd, tstack, bstack, kQueryThreads, dummy);   // RK:114
+        const TriHit h = trace_tlas<false, STK, PACKED, PAIRS, P16>(Tq, L, ro, rd, tstack, bstack, kQueryThreads, dummy, 0.0f, 0.0f, &vis);   // RK:114
         if (h.tri < 0) { missed = true; break; }                                     // RK:122-126: sampled after the loop
         if (bounce == 0) dist = h.t;                                                 // RK:116-118
         const float next = affect + sum;                                             // RK:120
@@ -68,7 +69,7 @@ __device__ __forceinline__ PathEnd path_triangles(const RtTriScene& T, const RtT
         const v3 diffuseColor = scale(s.w, s.rgb);                                   // RK:133
         const v3 samplerColor = scale(1.0f - s.w, tex2d_sample(T, s.u, s.v));        // RK:134
         const v3 albedo = add(diffuseColor, samplerColor);                           // RK:135, the sum
-        const TriHit sh = trace_tlas<false, STK, PACKED, PAIRS, P16>(Tq, L, sc.lightPos, sdir, tstack, bstack, kQueryThreads, dummy);   // RK:153
+        const TriHit sh = trace_tlas<false, STK, PACKED, PAIRS, P16>(Tq, L, sc.lightPos, sdir, tstack, bstack, kQueryThreads, dummy, 0.0f, 0.0f, &vis);   // RK:153
         float intensity = sc.minIntensity;                                           // RK:165
         if (sh.tri >= 0) {                                                           // RK:155
             const v3 hp = add(sc.lightPos, scale(sh.t, sdir));                       // RK:156

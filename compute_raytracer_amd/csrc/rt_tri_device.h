@@ -53,8 +53,11 @@ __device__ __forceinline__ NodeR load_node_head(const RtTriScene& T, const TriLd
 }
 // ROOTS = false: the caller never passes pair records with this form (ray queries without the instance data in their arguments) --
 // no dynamically indexed read of T.root_meta, which would copy the whole argument block to scratch.
+// mk (ray queries alone; null: a frame, which has no masks): word 18 of staged record k, the padding word that is left, carries the
+// visibility mask of instance k (trace_blas / multi_blas read it).  INST: the host put it there (rt_api.hip: tri_fill_inst).  Otherwise it is
+// written here from the device table, 0xFFFFFFFF beyond its length -- the caller's padding word is never read as a mask.
 template <int WAVES, uint32_t NODES = kLdsNodes, uint32_t BLAS = kLdsBlas, bool INST = false, bool ROOTS = true>
-__device__ __forceinline__ TriLds stage_head(const RtTriScene& T, float4* s_nodes, float* s_blas) {
+__device__ __forceinline__ TriLds stage_head(const RtTriScene& T, float4* s_nodes, float* s_blas, const RtQueryMask* mk = nullptr) {
     TriLds L;
     L.n_nodes = T.n_nodes < NODES ? T.n_nodes : NODES;
     L.n_blas = T.n_blas < BLAS ? T.n_blas : BLAS;
@@ -79,6 +82,10 @@ __device__ __forceinline__ TriLds stage_head(const RtTriScene& T, float4* s_node
     for (uint32_t i = threadIdx.x; i < 20u * L.n_blas; i += 64 * WAVES) {
         float v = (i % 20u == 19u && i / 20u < L.n_lookup) ? T.blas_lookup[i / 20u] : T.blas[i];
         if (ROOTS && T.pairs && i % 20u == 17u) v = __uint_as_float(T.root_meta[i / 20u]);
+        if (mk && i % 20u == 18u) {                                 // (stored as the integer it is: no float move of an all-ones word)
+            reinterpret_cast<uint32_t*>(s_blas)[i] = i / 20u < mk->n ? mk->table[i / 20u] : 0xFFFFFFFFu;
+            continue;
+        }
         s_blas[i] = v;
     }
     __syncthreads();
@@ -150,6 +157,14 @@ __device__ __forceinline__ bool hit_triangle(const RtTriScene& T, uint32_t slot,
     return false;
 }
 
+// Instance visibility (ray queries: rt_write_instance_masks, rt_set_query_masks).  One search's view: the mask of its ray and the
+// device table of instance masks.  Instance bi is visible iff (its mask & ray) != 0; a staged record carries its mask in word 18
+// (stage_head), a record that is not staged reads the table, and records beyond the table have 0xFFFFFFFF.
+// The mask word is read WITH the instance's record (trace_blas, multi_blas), in one batch of LDS (or global) reads: read on its own
+// in front of them it is a second dependent round trip per instance and ray, which the k-nearest walk at five waves per SIMD does
+// not hide.
+struct TriVis { const uint32_t* table; uint32_t n; uint32_t ray; };
+
 // RK:246-332 traceBLAS (the normal transform RK:334-338 is deferred to finish_hit)
 // STK: the element type of the traversal stacks.  uint16_t when the node buffer has at most 65,536 entries:
 // an index is stored clamped to the last node, which is what load_node makes of it anyway.
@@ -166,22 +181,28 @@ __device__ __forceinline__ bool hit_triangle(const RtTriScene& T, uint32_t slot,
 // both stacks, the staged heads and the instance records then take 7,616 bytes of LDS per wave and a fifth wave per SIMD fits.
 // LIMITS: `tmin` replaces 0.001 in the triangle test (ray queries, RT_QUERY_LIMITS).  ANY: the walk ends at the first accepted
 // triangle (occlusion queries); up to that step it is the nearest-hit walk, step for step.
+// vis (ray queries; null: every instance is visible): an instance the ray cannot see is left before anything is computed for it --
+// no ray transform, no box, no triangle; `nearest` and `hit` stay as they are.
 template <bool COUNT, typename STK, bool PACKED, bool PAIRS = false, bool P16 = false, bool LIMITS = false, bool ANY = false>
 __device__ __forceinline__ void trace_blas(const RtTriScene& T, const TriLds& L, uint32_t bi, v3 o, v3 d, float& nearest,
                                            TriHit& hit, typename std::conditional<PACKED && !P16, uint32_t, STK>::type* stack,
-                                           uint32_t stride, float& traces, float tmin = 0.0f) {
+                                           uint32_t stride, float& traces, float tmin = 0.0f, const TriVis* vis = nullptr) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     auto pack16 = [](uint32_t m) -> uint32_t { return ((m >> 16) << 14) | (m & 0x3FFFu); };
     auto unpack16 = [](uint32_t e) -> uint32_t { return ((e >> 14) << 16) | (e & 0x3FFFu); };
     float m[17];                                                    // mat4 column-major, m[4c + r]; m[16] root index
+    uint32_t mask = 0xFFFFFFFFu;                                    // (read only with vis)
     if (bi < L.n_blas) {
 #pragma unroll
         for (int k = 0; k < 17; ++k) m[k] = L.blas[20u * bi + (uint32_t)k];
+        if (vis) mask = __float_as_uint(L.blas[20u * bi + 18u]);
     } else {
         const float* g = T.blas + 20u * (size_t)bi;
 #pragma unroll
         for (int k = 0; k < 17; ++k) m[k] = g[k];
+        if (vis && bi < vis->n) mask = vis->table[bi];
     }
+    if (vis && (mask & vis->ray) == 0u) return;
     const v3 oo = V(((m[0] * o.x + m[4] * o.y) + m[8] * o.z) + m[12] * 1.0f,
                     ((m[1] * o.x + m[5] * o.y) + m[9] * o.z) + m[13] * 1.0f,
                     ((m[2] * o.x + m[6] * o.y) + m[10] * o.z) + m[14] * 1.0f);       // RK:254
@@ -298,11 +319,14 @@ __device__ __forceinline__ void trace_blas(const RtTriScene& T, const TriLds& L,
 // RK:168-244 traceTLAS.  tstack / bstack: this lane's two LDS stacks.
 // LIMITS: the search is (tmin, tmax) -- tmin replaces 0.001 in the triangle test and the running nearest hit starts at tmax
 // instead of 9999; box pruning is the reference's.  ANY: return at the first accepted triangle (see trace_blas).
+// vis (null: every instance is visible, and nothing of this is compiled -- the frame kernels): an instance the ray cannot see is left
+// out between the clamp of RK:223 and traceBLAS's first operation (trace_blas reads the mask with the record); the top-level walk is
+// untouched.
 template <bool COUNT, typename STK, bool PACKED, bool PAIRS = false, bool P16 = false, uint32_t TS = kStack, bool LIMITS = false,
           bool ANY = false>
 __device__ __forceinline__ TriHit trace_tlas(const RtTriScene& T, const TriLds& L, v3 o, v3 d, STK* tstack,
                                              typename std::conditional<PACKED && !P16, uint32_t, STK>::type* bstack, uint32_t stride, float& traces,
-                                             float tmin = 0.0f, float tmax = 0.0f) {
+                                             float tmin = 0.0f, float tmax = 0.0f, const TriVis* vis = nullptr) {
     TriHit hit; hit.t = 0.0f; hit.u = hit.v = 0.0f; hit.tri = -1; hit.blas = -1;   // RK:170-171
     float nearest = LIMITS ? tmax : 9999.0f;                        // RK:172
     const v3 inv = V(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
@@ -338,7 +362,7 @@ __device__ __forceinline__ TriHit trace_tlas(const RtTriScene& T, const TriLds& 
                 if (li >= T.n_blas_lookup) li = T.n_blas_lookup - 1u;
                 uint32_t bi = u32f(li < L.n_lookup ? L.blas[20u * li + 19u] : T.blas_lookup[li]);   // RK:223
                 if (bi >= T.n_blas) bi = T.n_blas - 1u;
-                trace_blas<COUNT, STK, PACKED, PAIRS, P16, LIMITS, ANY>(T, L, bi, o, d, nearest, hit, bstack, stride, traces, tmin);   // RK:221-230
+                trace_blas<COUNT, STK, PACKED, PAIRS, P16, LIMITS, ANY>(T, L, bi, o, d, nearest, hit, bstack, stride, traces, tmin, vis);   // RK:221-230
                 if (ANY && hit.tri >= 0) return hit;
             }
             if (sp == 0u) break;                                    // RK:233
@@ -413,7 +437,7 @@ __device__ __forceinline__ void instance_ray(const float* m, v3 o, v3 d, v3& oo,
 template <int K, typename STK, bool PACKED, bool PAIRS, bool P16>
 __device__ __forceinline__ void multi_blas(const RtTriScene& T, const TriLds& L, uint32_t bi, v3 o, v3 d, HitList<K, true>& list, uint32_t k,
                                            typename std::conditional<PACKED && !P16, uint32_t, STK>::type* stack, uint32_t stride,
-                                           float tmin, float tmax) {
+                                           float tmin, float tmax, const TriVis* vis = nullptr) {
     typedef typename std::conditional<PACKED && !P16, uint32_t, STK>::type BSTK;
     auto pack16 = [](uint32_t m) -> uint32_t { return ((m >> 16) << 14) | (m & 0x3FFFu); };
     auto unpack16 = [](uint32_t e) -> uint32_t { return ((e >> 14) << 16) | (e & 0x3FFFu); };
@@ -427,14 +451,18 @@ __device__ __forceinline__ void multi_blas(const RtTriScene& T, const TriLds& L,
         }
     };
     float m[17];                                                    // (as in trace_blas)
+    uint32_t mask = 0xFFFFFFFFu;
     if (bi < L.n_blas) {
 #pragma unroll
         for (int q = 0; q < 17; ++q) m[q] = L.blas[20u * bi + (uint32_t)q];
+        if (vis) mask = __float_as_uint(L.blas[20u * bi + 18u]);
     } else {
         const float* g = T.blas + 20u * (size_t)bi;
 #pragma unroll
         for (int q = 0; q < 17; ++q) m[q] = g[q];
+        if (vis && bi < vis->n) mask = vis->table[bi];
     }
+    if (vis && (mask & vis->ray) == 0u) return;
     v3 oo, od;
     instance_ray(m, o, d, oo, od);
     const v3 inv = V(1.0f / od.x, 1.0f / od.y, 1.0f / od.z);        // RK:396
@@ -514,11 +542,12 @@ __device__ __forceinline__ void multi_blas(const RtTriScene& T, const TriLds& L,
     }
 }
 
-// trace_tlas for the k nearest (twenty top-level slots, the guard of RK:212): fills `list`; the pruning rule is multi_blas's
+// trace_tlas for the k nearest (twenty top-level slots, the guard of RK:212): fills `list`; the pruning rule is multi_blas's; vis as
+// in trace_tlas
 template <int K, typename STK, bool PACKED, bool PAIRS, bool P16>
 __device__ __forceinline__ void multi_tlas(const RtTriScene& T, const TriLds& L, v3 o, v3 d, HitList<K, true>& list, uint32_t k, STK* tstack,
                                            typename std::conditional<PACKED && !P16, uint32_t, STK>::type* bstack, uint32_t stride,
-                                           float tmin, float tmax) {
+                                           float tmin, float tmax, const TriVis* vis = nullptr) {
     list.init(tmax);
     const v3 inv = V(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
     NodeR node = load_node_head(T, L, 0u);                          // RK:175
@@ -551,7 +580,7 @@ __device__ __forceinline__ void multi_tlas(const RtTriScene& T, const TriLds& L,
                 if (li >= T.n_blas_lookup) li = T.n_blas_lookup - 1u;
                 uint32_t bi = u32f(li < L.n_lookup ? L.blas[20u * li + 19u] : T.blas_lookup[li]);   // RK:223
                 if (bi >= T.n_blas) bi = T.n_blas - 1u;
-                multi_blas<K, STK, PACKED, PAIRS, P16>(T, L, bi, o, d, list, k, bstack, stride, tmin, tmax);
+                multi_blas<K, STK, PACKED, PAIRS, P16>(T, L, bi, o, d, list, k, bstack, stride, tmin, tmax, vis);
             }
             if (sp == 0u) break;
             sp -= 1u;

@@ -46,6 +46,23 @@ struct RtTriScene {
     uint32_t xcd_rows;         // set by the launch (no work list): workgroup b renders row (b % 8) + 8 (b / 8 / tiles per row) -- a row per XCD
 };
 
+// Instance visibility of a ray query (include/rt355.h: rt_write_instance_masks, rt_set_query_masks): the query kernels' own small
+// argument -- no frame kernel takes it, and RtTriScene / RtTriInst hold none of it.  Instance bi (a BLAS record) is visible to a ray
+// iff (mask of bi) & (mask of the ray) != 0.
+struct RtQueryMask {
+    const uint32_t* table;     // [n] the mask of record i, device memory (null with n == 0); records from n on: 0xFFFFFFFF
+    uint32_t n;
+    uint32_t nearest;          // the mask of every nearest-hit search of the call
+    uint32_t occlusion;        // ... and of its any-hit searches (rt_occluded, the k rays of rt_render_ao)
+};
+// The scene of a ray query: what a frame's kernel takes, and the masks of the call beside it.  Every rt_launch_*_triangles function
+// of the queries below is handed one of these through its `const RtTriScene& t` (rt_api.hip: Query::ts) -- the launch signatures
+// are those of the unmasked queries -- and passes the two parts to its kernel as two arguments.
+struct RtQueryScene : RtTriScene {
+    RtQueryMask mask;
+};
+inline const RtQueryMask& rt_query_mask_of(const RtTriScene& t) { return static_cast<const RtQueryScene&>(t).mask; }
+
 // Which stack form rt_launch_triangles runs the frame as: 0 twenty TLAS slots, 1 four (five waves per SIMD), 2 three (six waves),
 // 3 eight (five waves), 4 eight with sixteen staged instances.  The caller stores the answer in t.form before the launch and, for
 // 1 - 4, fills t.inst.
@@ -59,6 +76,8 @@ hipError_t rt_launch_order_scatter(uint32_t* cost, uint32_t* scan, uint32_t* ord
 hipError_t rt_launch_tri_corners(float4* out, const float* tri, const float* lookup, uint32_t n_slots, uint32_t n_tri, hipStream_t s);
 // Ray queries (rt_query.hip; include/rt355.h: rt_trace_rays): rays [n][2] float4 {origin, -}, {dir, -}, hits [n][2] float4 (rt_hit).
 // inst: the instance data travels in t.inst (stage_head<..., true>), as for the small forms; t.pairs only with inst.
+// t: an RtQueryScene, in every triangle launch below: the instance masks and the ray masks of the call travel in its `mask` (with
+// inst, word 18 of record k of t.inst.blas holds the mask of instance k).
 hipError_t rt_launch_query_triangles(const RtTriScene& t, int inst, const float4* rays, float4* hits, uint32_t n, hipStream_t s);
 hipError_t rt_launch_query_spheres(const float* records, uint32_t n_spheres, const float4* rays, float4* hits, uint32_t n, hipStream_t s);
 // RT_QUERY_LIMITS in `flags`: (tmin, tmax) from ray words 3 and 7.  any: one byte per ray (rt_occluded), else rt_hit records

@@ -290,6 +290,52 @@ class RendererRaytracing:
                   self._ctx)
         return occ.astype(bool)
 
+    # ---- instance visibility masks (rt_write_instance_masks / rt_set_query_masks): ray queries alone, frames ignore them -----
+    def set_instance_masks(self, masks):
+        """One 32-bit visibility mask per instance, in scene.instances order (the BLAS record order, rt_hit.instance): a sequence
+        or array of integers in [0, 2**32).  Instances beyond the sequence keep 0xFFFFFFFF; None clears the table.  An instance
+        is visible to a ray iff (its mask & the ray's mask) != 0 (set_query_masks).  The table belongs to no scene buffer: it
+        survives every scene write.  Waits for the queries enqueued before it; frames in flight go on."""
+        m = self._pack_masks(masks)
+        abi.check(self._lib.rt_write_instance_masks(self._ctx, m.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)) if m.size else None,
+                                                    m.size), self._ctx)
+
+    def set_query_masks(self, nearest=0xFFFFFFFF, occlusion=0xFFFFFFFF):
+        """The masks the rays of later queries carry, copied at each query call.  `nearest`: trace_rays, trace_rays_multi, pick,
+        render_gbuffer, the primary ray of render_ao and every ray of shade_rays and render_samples.  `occlusion`: occluded and
+        the k rays of render_ao."""
+        masks = []
+        for name, value in (("nearest", nearest), ("occlusion", occlusion)):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not 0 <= int(value) < 2 ** 32:
+                raise ValueError("set_query_masks: %s must be an integer in [0, 2**32)" % name)
+            masks.append(int(value))
+        abi.check(self._lib.rt_set_query_masks(self._ctx, masks[0], masks[1]), self._ctx)
+
+    @staticmethod
+    def _pack_masks(masks):
+        """(n,) uint32, C-contiguous: the table rt_write_instance_masks takes.  None: the empty table.  Anything that is not a
+        one-dimensional sequence of integers in [0, 2**32) raises ValueError."""
+        if masks is None:
+            return np.zeros(0, dtype=np.uint32)
+        if isinstance(masks, (str, bytes)):
+            raise ValueError("set_instance_masks: masks must be a sequence of integers")
+        try:
+            a = np.asarray(masks)
+        except Exception:
+            raise ValueError("set_instance_masks: masks must be a sequence of integers")
+        if a.ndim != 1:
+            raise ValueError("set_instance_masks: masks must be one-dimensional, one integer per instance")
+        if a.size == 0:
+            return np.zeros(0, dtype=np.uint32)
+        if a.dtype == object:                   # Python integers too large for any fixed dtype, or a mixed sequence
+            if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in a):
+                raise ValueError("set_instance_masks: masks must be integers")
+        elif a.dtype.kind not in "iu":
+            raise ValueError("set_instance_masks: masks must be integers, not %s" % a.dtype)
+        if any(int(v) < 0 or int(v) >= 2 ** 32 for v in a):
+            raise ValueError("set_instance_masks: every mask must be in [0, 2**32)")
+        return np.ascontiguousarray(np.array([int(v) for v in a], dtype=np.uint64).astype(np.uint32))
+
     @staticmethod
     def _pack_rays(origins, directions, tmin, tmax):
         """(n, 8) float32 rays {origin, tmin, dir, tmax}"""

@@ -519,6 +519,41 @@ typedef struct rt_ao {
 int rt_render_ao(rt_ctx* ctx, const uint32_t* rect, const float* dirs, uint32_t k, float tmin, float radius, const rt_ao* out, size_t cap_pixels, void* hip_stream); /* device, async */
 int rt_render_ao_host(rt_ctx* ctx, const uint32_t* rect, const float* dirs, uint32_t k, float tmin, float radius, const rt_ao* out, size_t cap_pixels);             /* host, sync   */
 
+/* ---- instance visibility masks: which instances the rays of a query may see --------------------------------------------------- */
+
+/* rt_write_instance_masks / rt_set_query_masks: every instance has a 32-bit mask, every ray a query casts carries one, and an
+ * instance is visible to a ray if and only if (instance mask & ray mask) != 0.  An instance is a BLAS record: its index bi is the
+ * value of RK:223 after the library's clamp to n_blas - 1, the number rt_hit.instance reports.  A ray never enters the BLAS of an
+ * instance it cannot see -- no ray transform, no box test and no triangle test there.  The top-level walk does not change: its box
+ * tests, its order, its stack, the guard of RK:212 and the running nearest hit are what they are without masks.  With every mask at
+ * its default, 0xFFFFFFFF, every query returns the bits it returns without this section.  Sphere scenes have no instances: the masks
+ * are kept and ignored, and every sphere stays visible.
+ *
+ * rt_write_instance_masks: `masks` is HOST memory, n words, copied before the call returns.  Record i < n takes masks[i]; records
+ * from n on have 0xFFFFFFFF.  n == 0 clears the table (`masks` may then be NULL).
+ *   - The table indexes records, not models, and belongs to no scene buffer: it survives rt_write_blas, rt_write_blas_lookup,
+ *     per-frame instance writes, rt_refit_blas and rt_build_blas, whatever the record count becomes.  It may be written before any
+ *     scene, and on a context that holds spheres.
+ *   - For queries it is a scene write: a query sees every mask write made before it, on any stream.  The write waits for the queries
+ *     enqueued before it, and those keep the table they were enqueued with.
+ *   - No frame reads the table: the write does not drain, does not wait for frames and does not disturb them.
+ *   - Checks, in this order: a NULL context, then n > 0 with NULL `masks`: RT_ERR_INVALID_ARG.
+ *
+ * rt_set_query_masks: the two ray masks of the context, both 0xFFFFFFFF until set.  They are copied at each query call, as the
+ * parameters are: a later change does not reach a query already enqueued.  A NULL context: RT_ERR_INVALID_ARG.
+ *   - `nearest` is the mask of every nearest-hit search: rt_trace_rays, _host, _ex, _host_ex; rt_trace_rays_multi, _host; rt_pick;
+ *     rt_render_gbuffer, _host; the primary ray of rt_render_ao, _host; and every ray of rt_shade_rays, _host and rt_render_samples,
+ *     _host -- path rays and shadow rays alike, the reference's shadow test (RK:147-165) being a nearest-hit search.
+ *   - `occlusion` is the mask of rt_occluded, _host and of the k rays of rt_render_ao, _host.
+ *   - With both masks equal, occluded[i] = 1 if and only if rt_trace_rays_ex reports a hit for ray i, as without masks; every
+ *     relation between the queries stated above holds among queries that carry the same mask.
+ *
+ * Frames ignore both: rt_render, rt_render_to, rt_render_gather, rt_group_render and the heatmap see every instance, and their
+ * rt_stats are what they are without masks.  A masked frame is rt_render_samples with s = 1.  No entry point above gains a flag bit;
+ * there are no per-ray masks. */
+int rt_write_instance_masks(rt_ctx* ctx, const uint32_t* masks, uint32_t n);   /* host memory */
+int rt_set_query_masks(rt_ctx* ctx, uint32_t nearest, uint32_t occlusion);
+
 /* ---- multi-GPU: render + RCCL gather behind one call (RR:434-470 across a group of GPUs) ------ */
 
 /* One process per GPU.  Rank 0 calls rt_comm_unique_id and hands the bytes to the other ranks by

@@ -17,7 +17,10 @@ through rt_render -- the same pixels by both routes -- on the reference's scene 
 spheres by brute force, the frame walks the hierarchy).
 "samples_ref_s2" ... "samples_c3_s4": rt_render_samples (both outputs) of a 1024 x 1024 frame at s = 2 and 4, beside (a) rt_shade_rays
 with RT_SHADE_COMPOSE over the same s*s 2^20 rays resident on the device and (b) kernel_ms of an rt_render frame of
-(1024 s) x (1024 s) -- the same samples by the three routes.  `python tools/query_rate.py samples` runs these alone."""
+(1024 s) x (1024 s) -- the same samples by the three routes.  `python tools/query_rate.py samples` runs these alone.
+`python tools/query_rate.py ref` runs "ref_primary" and "ref_random_2^20" alone, for nearest, limited, occluded, shade and multi4:
+the A/B of two builds (RT355_LIB), a run each in turn.  `python tools/query_rate.py ref hide` does so with an instance mask table
+that hides every instance of the reference scene's largest mesh (rt_write_instance_masks): what a skipped instance saves."""
 import json
 import os
 import sys
@@ -93,9 +96,12 @@ def timed_one(torch, r, rays, kind):
     return {"ms": round(ms, 4), "rays_per_ms": round(rays.shape[0] / ms), "hit_fraction": round(hits / rays.shape[0], 3)}
 
 
-def timed(torch, r, rays):
+KINDS = ("nearest", "limited", "occluded", "shade", "multi1", "multi4", "multi8")
+
+
+def timed(torch, r, rays, kinds=KINDS):
     res = {"rays": int(rays.shape[0])}
-    for kind in ("nearest", "limited", "occluded", "shade", "multi1", "multi4", "multi8"):
+    for kind in kinds:
         res[kind] = timed_one(torch, r, rays, kind)
     return res
 
@@ -168,6 +174,25 @@ def samples(torch, out):
         out["samples_c3_s%d" % s] = samples_vs_routes(torch, c3, cfg["bounces"], None, s)
 
 
+def largest_mesh(scene):
+    """The mesh with the most lookup slots under its BLAS root, and that count"""
+    nodes = np.asarray(scene.pack_blas_nodes(), np.float32).reshape(-1, 8)
+
+    def slots(root):
+        total, todo = 0, [int(root) - scene.tlasNodesMax]
+        while todo:
+            i = todo.pop()
+            left, count = int(nodes[i, 3]) - scene.tlasNodesMax, int(nodes[i, 7])
+            if count:
+                total += count
+            else:
+                todo += [left, left + 1]
+        return total
+
+    sizes = [slots(m.root_node) for m in scene.meshes]
+    return int(np.argmax(sizes)), max(sizes)
+
+
 def main():
     import torch
     if sys.argv[1:] == ["samples"]:
@@ -175,6 +200,7 @@ def main():
         samples(torch, out)
         print(json.dumps(out))
         return
+    ref_only = sys.argv[1:2] == ["ref"]
     d = np.load(os.path.join(ROOT, "tests", "golden", "ref_scene.npz"))
     scene = rt.SceneRaytracing.from_packed(d)
     W, H = int(d["W"]), int(d["H"])
@@ -184,12 +210,22 @@ def main():
         r.render()
     st = r.stats()
     out["ref_frame"] = {"rays": st["rays"], "kernel_ms": round(st["kernel_ms"], 4), "rays_per_ms": round(st["rays"] / st["kernel_ms"])}
-    out["ref_primary"] = timed(torch, r, ray_tensor(torch, *camera(scene, W, H)))
+    kinds = ("nearest", "limited", "occluded", "shade", "multi4") if ref_only else KINDS
+    if sys.argv[1:] == ["ref", "hide"]:
+        mesh, n_slots = largest_mesh(scene)
+        hidden = np.asarray(scene.instances.mesh_index) == mesh
+        r.set_instance_masks(np.where(hidden, 0, 0xFFFFFFFF))
+        out["hidden"] = {"mesh": mesh, "slots": n_slots, "instances": [int(i) for i in np.nonzero(hidden)[0]]}
+    out["ref_primary"] = timed(torch, r, ray_tensor(torch, *camera(scene, W, H)), kinds)
     root = np.asarray(scene.pack_tlas_nodes(), np.float64).reshape(-1, 8)[0]
     cam = scene.pack_params(4)[0:3].astype(np.float64)                  # (the floor's box spans millions: within 20 of the camera)
     lo, hi = np.maximum(root[0:3], cam - 20.0), np.minimum(root[4:7], cam + 20.0)
-    out["ref_random_2^20"] = timed(torch, r, ray_tensor(torch, *random_rays(lo, hi, 1 << 20, 1)))
+    out["ref_random_2^20"] = timed(torch, r, ray_tensor(torch, *random_rays(lo, hi, 1 << 20, 1)), kinds)
     r.close()
+    if ref_only:
+        out["build_id"] = rt.abi.load().rt_build_id().decode()
+        print(json.dumps(out))
+        return
     cfg = rt.BASELINE_CONFIGS["C3"]
     c3 = rt.synthetic_scene(cfg["spheres"], cfg["seed"])
     r = rt.RendererRaytracing(256, 256, c3, maxBounces=cfg["bounces"]).initialize()
