@@ -7,7 +7,7 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-fast-math -Wall -Wn
 SRCS     := $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h)) include/rt355.h
 # identity of the build: profiles (profiles/traffic.json) are evidence for the sources they were taken with
 BUILD_ID := $(shell cat $(SRCS) | sha256sum | cut -c1-16)
-OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o $(CSRC)/rt_query.o $(CSRC)/rt_shade.o $(CSRC)/rt_sample.o $(CSRC)/rt_gbuffer.o $(CSRC)/rt_ao.o $(CSRC)/rt_refit.o $(CSRC)/rt_build.o
+OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o $(CSRC)/rt_query.o $(CSRC)/rt_shade.o $(CSRC)/rt_sample.o $(CSRC)/rt_gbuffer.o $(CSRC)/rt_ao.o $(CSRC)/rt_refit.o $(CSRC)/rt_build.o $(CSRC)/rt_tlas.o
 
 all: lib oracle node
 
@@ -51,6 +51,11 @@ $(CSRC)/rt_refit.o: $(CSRC)/rt_refit.hip $(CSRC)/rt_refit.h
 # the device BLAS build: float64 planes, areas and costs that must equal the host builder's bit for bit -- no FMA contraction, no
 # SLP vectorisation (exactness rests on them); rt_blas_build.h holds the arithmetic and is shared with the host model
 $(CSRC)/rt_build.o: $(CSRC)/rt_build.hip $(CSRC)/rt_build.h $(CSRC)/rt_blas_build.h include/rt355.h
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
+
+# the device top-level build's front end: float64 cofactors and corner transforms that must equal the host model's bit for bit;
+# rt_build.o's flags exactly.  rt_tlas_build.h holds the arithmetic and is shared with the host model
+$(CSRC)/rt_tlas.o: $(CSRC)/rt_tlas.hip $(CSRC)/rt_tlas_build.h $(CSRC)/rt_build.h $(CSRC)/rt_blas_build.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/rt_assemble.o: $(CSRC)/rt_assemble.hip $(CSRC)/rt_types.h include/rt355.h

@@ -50,6 +50,7 @@ SYMBOLS = [
     "rt_update_triangles", "rt_refit_blas", "rt_read_nodes", "rt_refit_plan",
     "rt_build_blas", "rt_read_tri_lookup", "rt_build_blas_host",
     "rt_write_instance_masks", "rt_set_query_masks",
+    "rt_build_tlas", "rt_build_tlas_device", "rt_build_tlas_host", "rt_read_blas", "rt_read_blas_lookup",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -106,6 +107,11 @@ class RtBlasRange(ctypes.Structure):
 
 # the same record as a numpy dtype: an (n,) array of it is what rt_build_blas takes
 BLAS_RANGE_DTYPE = [("root_node", "<u4"), ("node_cap", "<u4"), ("first_slot", "<u4"), ("n_slots", "<u4")]
+
+
+class RtTlasInfo(ctypes.Structure):
+    """rt_tlas_info (include/rt355.h): the tree rt_build_tlas made, 16 bytes."""
+    _fields_ = [("nodes_used", ctypes.c_uint32), ("depth", ctypes.c_uint32), ("leaves", ctypes.c_uint32), ("max_leaf", ctypes.c_uint32)]
 
 
 class RtAo(ctypes.Structure):
@@ -240,6 +246,11 @@ def load():
         "rt_build_blas_host": (ctypes.c_int, [fp, u32, fp, u32, fp, u32, ctypes.POINTER(RtBlasRange), u32, ctypes.POINTER(u32)]),
         "rt_write_instance_masks": (ctypes.c_int, [vp, ctypes.POINTER(u32), u32]),
         "rt_set_query_masks": (ctypes.c_int, [vp, u32, u32]),
+        "rt_build_tlas": (ctypes.c_int, [vp, fp, ctypes.POINTER(u32), u32, u32, ctypes.POINTER(RtTlasInfo)]),
+        "rt_build_tlas_device": (ctypes.c_int, [vp, vp, ctypes.POINTER(u32), u32, u32, ctypes.POINTER(RtTlasInfo), vp]),
+        "rt_build_tlas_host": (ctypes.c_int, [fp, ctypes.POINTER(u32), u32, fp, u32, fp, fp, fp, u32, ctypes.POINTER(RtTlasInfo)]),
+        "rt_read_blas": (ctypes.c_int, [vp, u32, u32, fp]),
+        "rt_read_blas_lookup": (ctypes.c_int, [vp, u32, u32, fp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

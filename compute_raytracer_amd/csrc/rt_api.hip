@@ -20,6 +20,7 @@
 #include "rt_refit.h"
 #include "rt_refit_plan.h"
 #include "rt_build.h"
+#include "rt_tlas_build.h"
 #include "rt_tlas_fit.h"
 
 thread_local std::string g_rt_err;
@@ -1676,6 +1677,31 @@ int rt_build_blas_host(const float* triangles, uint32_t n_triangles, float* tri_
     return RT_OK;
 }
 
+// The levels of a build whose level 0 (`n_roots` nodes) the prep pass has made: price, scan and split per level -- the host learns
+// one word per level, the next level's node count -- and then the splits per subtree, last level first.  off / cnt: where each
+// level lies among the build nodes; the last entry is the empty level.
+static int build_levels(const char* who, const RtBuildArgs& ba, uint32_t n_roots, hipStream_t s, std::vector<uint32_t>& off, std::vector<uint32_t>& cnt) {
+    off.assign(1, 0u);
+    cnt.assign(1, n_roots);
+    while (cnt.back() != 0u) {
+        const uint32_t level = (uint32_t)cnt.size() - 1u;
+        RT_HIP(rt_launch_build_level(ba, level, off[level], cnt[level], s));
+        uint32_t next = 0u;
+        RT_HIP(hipMemcpyAsync(&next, ba.next_count, 4u, hipMemcpyDeviceToHost, s));
+        RT_HIP(hipStreamSynchronize(s));
+        const uint32_t o = off[level] + cnt[level];
+        if (next > ba.node_cap - o) {
+            char msg[200];
+            std::snprintf(msg, sizeof msg, "%s: a level beyond the build's node capacity (corrupt scratch state)", who);
+            return fail(RT_ERR_HIP, msg);
+        }
+        off.push_back(o);
+        cnt.push_back(next);
+    }
+    for (uint32_t l = (uint32_t)cnt.size() - 1u; l-- > 0u;) RT_HIP(rt_launch_build_count_up(ba, off[l], cnt[l], s));
+    return RT_OK;
+}
+
 int rt_build_blas(rt_ctx* c, const rt_blas_range* ranges, uint32_t n, uint32_t* used) {
     if (!c || (!ranges && n)) return fail(RT_ERR_INVALID_ARG, "rt_build_blas: NULL argument");
     const uint32_t n_nodes = (uint32_t)(c->nodes_used / 32u), n_slots = (uint32_t)(c->d_tri_lookup.used / 4u);
@@ -1726,20 +1752,9 @@ int rt_build_blas(rt_ctx* c, const rt_blas_range* ranges, uint32_t n, uint32_t* 
     RT_HIP(hipStreamSynchronize(s));                    // a pageable source
     // ---- the levels: the host learns one word per level, the next level's node count ----
     RT_HIP(rt_launch_build_prep(ba, ranges, s));
-    std::vector<uint32_t> off(1, 0u), cnt(1, n);
-    while (cnt.back() != 0u) {
-        const uint32_t level = (uint32_t)cnt.size() - 1u;
-        RT_HIP(rt_launch_build_level(ba, level, off[level], cnt[level], s));
-        uint32_t next = 0u;
-        RT_HIP(hipMemcpyAsync(&next, ba.next_count, 4u, hipMemcpyDeviceToHost, s));
-        RT_HIP(hipStreamSynchronize(s));
-        const uint32_t o = off[level] + cnt[level];
-        if (next > node_cap - o) return fail(RT_ERR_HIP, "rt_build_blas: a level beyond the build's node capacity (corrupt scratch state)");
-        off.push_back(o);
-        cnt.push_back(next);
-    }
+    std::vector<uint32_t> off, cnt;
+    { int rc = build_levels("rt_build_blas", ba, n, s, off, cnt); if (rc != RT_OK) return rc; }
     const uint32_t levels = (uint32_t)cnt.size() - 1u;  // the last entry is the empty level
-    for (uint32_t l = levels; l-- > 0u;) RT_HIP(rt_launch_build_count_up(ba, off[l], cnt[l], s));
     // ---- sizing before committing: nothing of the scene has been written so far ----
     std::vector<uint32_t> sub(n);
     RT_HIP(hipMemcpyAsync(sub.data(), ba.sub, (size_t)n * 4u, hipMemcpyDeviceToHost, s));
@@ -1792,6 +1807,137 @@ int rt_read_tri_lookup(rt_ctx* c, uint32_t first_slot, uint32_t n, float* dst) {
     RT_HIP(hipMemcpyAsync(dst, static_cast<const char*>(c->d_tri_lookup.p) + (size_t)first_slot * 4u, (size_t)n * 4u, hipMemcpyDeviceToHost, c->stream));
     RT_HIP(hipStreamSynchronize(c->stream));
     return RT_OK;
+}
+
+// ---- device top-level builds (rt_tlas_build.h: the arithmetic and the host model; rt_tlas.hip: the front end of rt_build.hip) ----
+
+int rt_build_tlas_host(const float* models, const uint32_t* roots, uint32_t n, const float* nodes, uint32_t n_nodes,
+                       float* tlas_nodes, float* blas, float* blas_lookup, uint32_t node_cap, rt_tlas_info* info) {
+    const char* why = "";
+    const int rc = rt_tl_build_host(models, roots, n, nodes, n_nodes, tlas_nodes, blas, blas_lookup, node_cap, info, &why);
+    if (rc != RT_OK) { char msg[200]; std::snprintf(msg, sizeof msg, "rt_build_tlas_host: %s", why); return fail(rc, msg); }
+    return RT_OK;
+}
+
+// models: host memory (device == false) or device memory the caller's stream `hip_stream` produced
+static int build_tlas(rt_ctx* c, const char* who, const float* models, bool device, void* hip_stream, const uint32_t* roots, uint32_t n,
+                      uint32_t node_cap, rt_tlas_info* info) {
+    char msg[200];
+    if (!c || !models || !roots) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (device && (reinterpret_cast<uintptr_t>(models) & 15u)) { std::snprintf(msg, sizeof msg, "%s: models_dev must be 16-byte aligned", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    const uint32_t n_nodes = (uint32_t)(c->nodes_used / 32u);
+    if (c->scene_kind != 1 || !n_nodes) {
+        std::snprintf(msg, sizeof msg, "%s: no triangle scene (rt_write_nodes first: the roots' boxes are read from it)", who);
+        return fail(RT_ERR_STATE, msg);
+    }
+    if (const char* bad = rt_tl_check_args(roots, n, node_cap, n_nodes)) { std::snprintf(msg, sizeof msg, "%s: %s", who, bad); return fail(RT_ERR_INVALID_ARG, msg); }
+    RT_HIP(hipSetDevice(c->device));
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    { int rc = grow_buf(c, c->d_nodes[0], c->nodes_used); if (rc != RT_OK) return rc; }
+    hipStream_t s = c->stream;
+    if (c->scene_stream && c->scene_stream != s) RT_HIP(hipStreamWaitEvent(s, c->ev_scene, 0));
+    if (device && hip_stream) RT_HIP(hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)));
+    // a root inside the head of the node buffer may so far live only in the copy that frames carry: version 0 (nothing is in
+    // flight) takes the host's current state first, as it does for a query (query_prepare)
+    if (c->ver_gen[0] != c->inst.gen && *std::min_element(roots, roots + n) < c->inst.head_nodes) {
+        int rc = apply_version(c, 0u, 0u, s);
+        if (rc != RT_OK) return rc;
+    }
+    // ---- scratch: everything is built aside; 2 n - 1 build nodes always suffice ----
+    const uint32_t cap = 2u * n - 1u;
+    size_t at = 0;
+    auto carve = [&](size_t bytes) { const size_t o = at; at += (bytes + 15u) & ~(size_t)15u; return o; };
+    const size_t o_range = carve(sizeof(rt_blas_range)), o_models = carve(device ? 0u : (size_t)n * 64u), o_roots = carve((size_t)n * 4u);
+    const size_t o_blas = carve((size_t)n * 80u), o_lookup = carve((size_t)n * 4u), o_nodes = carve((size_t)cap * 32u);
+    const size_t o_prim = carve((size_t)n * sizeof(RtBbPrim));
+    const size_t o_ord0 = carve((size_t)n * 4u), o_ord1 = carve((size_t)n * 4u), o_final = carve((size_t)n * 4u);
+    const size_t o_node = carve((size_t)cap * sizeof(RtBuildNode)), o_dec = carve((size_t)cap * sizeof(RtBuildDec));
+    const size_t o_sub = carve((size_t)cap * 4u), o_rank = carve((size_t)cap * 4u), o_index = carve((size_t)cap * 4u);
+    const size_t o_root = carve((size_t)cap * 4u), o_next = carve(4u);
+    { int rc = grow_buf(c, c->d_build, at); if (rc != RT_OK) return rc; }
+    char* base = static_cast<char*>(c->d_build.p);
+    const rt_blas_range range = {0u, cap, 0u, n};
+    RtBuildArgs ba;
+    ba.tri = nullptr; ba.n_tri = 0u;
+    ba.lookup = reinterpret_cast<float*>(base + o_lookup); ba.n_slots = n;
+    for (uint32_t v = 0; v < kBuildVersions; ++v) ba.nodes[v] = nullptr;
+    ba.nodes[0] = reinterpret_cast<float*>(base + o_nodes); ba.n_nodes = cap;
+    ba.ranges = reinterpret_cast<const rt_blas_range*>(base + o_range); ba.n_ranges = 1u;
+    ba.prim = reinterpret_cast<RtBbPrim*>(base + o_prim);
+    ba.order[0] = reinterpret_cast<uint32_t*>(base + o_ord0); ba.order[1] = reinterpret_cast<uint32_t*>(base + o_ord1);
+    ba.final_order = reinterpret_cast<uint32_t*>(base + o_final);
+    ba.node = reinterpret_cast<RtBuildNode*>(base + o_node); ba.dec = reinterpret_cast<RtBuildDec*>(base + o_dec);
+    ba.sub = reinterpret_cast<uint32_t*>(base + o_sub); ba.rank = reinterpret_cast<uint32_t*>(base + o_rank);
+    ba.index = reinterpret_cast<uint32_t*>(base + o_index); ba.root = reinterpret_cast<uint32_t*>(base + o_root);
+    ba.node_cap = cap;
+    ba.next_count = reinterpret_cast<uint32_t*>(base + o_next);
+    ba.inst.models = device ? models : reinterpret_cast<const float*>(base + o_models);
+    ba.inst.roots = reinterpret_cast<const uint32_t*>(base + o_roots);
+    ba.inst.nodes = static_cast<const float*>(c->d_nodes[0].p);
+    ba.inst.n_nodes = std::min(n_nodes, (uint32_t)(c->d_nodes[0].cap / 32u));
+    ba.inst.blas = reinterpret_cast<float*>(base + o_blas);
+    RT_HIP(hipMemcpyAsync(base + o_range, &range, sizeof range, hipMemcpyHostToDevice, s));
+    if (!device) RT_HIP(hipMemcpyAsync(base + o_models, models, (size_t)n * 64u, hipMemcpyHostToDevice, s));
+    RT_HIP(hipMemcpyAsync(base + o_roots, roots, (size_t)n * 4u, hipMemcpyHostToDevice, s));
+    RT_HIP(hipStreamSynchronize(s));                    // pageable sources
+    // ---- the levels: the host learns one word per level, the next level's node count ----
+    RT_HIP(rt_launch_build_prep(ba, &range, s));            // a.inst is set: rt_tlas.hip makes the prims
+    std::vector<uint32_t> off, cnt;
+    { int rc = build_levels(who, ba, 1u, s, off, cnt); if (rc != RT_OK) return rc; }
+    const uint32_t levels = (uint32_t)cnt.size() - 1u, used = off.back();       // every build node becomes one node of the tree
+    for (uint32_t l = 0; l < levels; ++l) RT_HIP(rt_launch_build_rank_down(ba, off[l], cnt[l], s));
+    for (uint32_t l = 0; l < levels; ++l) RT_HIP(rt_launch_build_emit_nodes(ba, off[l], cnt[l], s));
+    RT_HIP(rt_launch_build_emit_lookup(ba, &range, s));
+    // ---- read back, judge, and only then commit: as the three writes of the same bytes ----
+    std::vector<float> h_nodes((size_t)std::max(used, node_cap) * 8u, 0.0f), h_blas((size_t)n * 20u), h_lookup(n);
+    RT_HIP(hipMemcpyAsync(h_nodes.data(), base + o_nodes, (size_t)used * 32u, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipMemcpyAsync(h_blas.data(), base + o_blas, (size_t)n * 80u, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipMemcpyAsync(h_lookup.data(), base + o_lookup, (size_t)n * 4u, hipMemcpyDeviceToHost, s));
+    RT_HIP(hipStreamSynchronize(s));
+    const rt_tlas_info got = rt_tl_info(h_nodes.data(), used);
+    if (info) *info = got;
+    const char* why = "";
+    if (const int rc = rt_tl_verdict(got, node_cap, &why)) {
+        std::snprintf(msg, sizeof msg, "%s: %s (%u nodes, depth %u; node_cap %u)", who, why, got.nodes_used, got.depth, node_cap);
+        return fail(rc, msg);
+    }
+    { int rc = rt_write_blas(c, h_blas.data(), n); if (rc != RT_OK) return rc; }
+    { int rc = rt_write_blas_lookup(c, h_lookup.data(), n); if (rc != RT_OK) return rc; }
+    return rt_write_nodes(c, 0, h_nodes.data(), node_cap);
+}
+
+int rt_build_tlas(rt_ctx* c, const float* models, const uint32_t* roots, uint32_t n, uint32_t node_cap, rt_tlas_info* info) {
+    return build_tlas(c, "rt_build_tlas", models, false, nullptr, roots, n, node_cap, info);
+}
+int rt_build_tlas_device(rt_ctx* c, const float* models_dev, const uint32_t* roots, uint32_t n, uint32_t node_cap, rt_tlas_info* info,
+                         void* hip_stream) {
+    return build_tlas(c, "rt_build_tlas_device", models_dev, true, hip_stream, roots, n, node_cap, info);
+}
+
+// the BLAS records / the BLAS lookup words the next frame would read: the host's per-frame copy where frames carry it, else version 0
+static int read_instances(rt_ctx* c, const char* who, bool on, const std::vector<float>& carried, const rt_ctx::DevBuf& dev, uint32_t words,
+                          uint32_t first, uint32_t n, float* dst) {
+    char msg[160];
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    const size_t have = on ? carried.size() / words : dev.used / (4u * (size_t)words);
+    if ((uint64_t)first + n > have) { std::snprintf(msg, sizeof msg, "%s: first + n is beyond what was written", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (n == 0u) return RT_OK;
+    if (!dst) { std::snprintf(msg, sizeof msg, "%s: dst is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    RT_HIP(hipSetDevice(c->device));
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    if (on) { std::memcpy(dst, &carried[(size_t)first * words], (size_t)n * words * 4u); return RT_OK; }
+    if (c->scene_stream && c->scene_stream != c->stream) RT_HIP(hipStreamWaitEvent(c->stream, c->ev_scene, 0));
+    RT_HIP(hipMemcpyAsync(dst, static_cast<const char*>(dev.p) + (size_t)first * words * 4u, (size_t)n * words * 4u, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+int rt_read_blas(rt_ctx* c, uint32_t first, uint32_t n, float* dst) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_read_blas: ctx is NULL");
+    return read_instances(c, "rt_read_blas", c->inst.blas_on, c->inst.blas, c->d_blas[0], 20u, first, n, dst);
+}
+int rt_read_blas_lookup(rt_ctx* c, uint32_t first, uint32_t n, float* dst) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_read_blas_lookup: ctx is NULL");
+    return read_instances(c, "rt_read_blas_lookup", c->inst.lookup_on, c->inst.lookup, c->d_blas_lookup[0], 1u, first, n, dst);
 }
 
 int rt_filter_plan(const float* records, uint32_t n, const float params[24], int* filter_ok, int* signed_filter) {

@@ -21,6 +21,15 @@ struct RtBuildDec {                          // what price decided, 80 bytes
     uint32_t pad[2];
 };
 
+// The other front end (rt_tlas.hip, rt_build_tlas): the primitives of the one range are INSTANCES -- their padded world boxes --
+// instead of triangles.  models == nullptr: triangles.
+struct RtBuildInstances {
+    const float* models;                     // n_slots x 16 floats, column-major, 16-byte aligned
+    const uint32_t* roots;                   // n_slots root node indices
+    const float* nodes; uint32_t n_nodes;    // the node buffer the roots index (one version of it)
+    float* blas;                             // out: n_slots x 20 floats, 16-byte aligned
+};
+
 struct RtBuildArgs {
     // the scene
     const float* tri; uint32_t n_tri;        // 40-float records
@@ -40,10 +49,12 @@ struct RtBuildArgs {
     uint32_t* root;                          // the root_node of the node's tree
     uint32_t node_cap;
     uint32_t* next_count;                    // one word: the node count of the next level
+    RtBuildInstances inst = {};
 };
 
 // h_ranges: the host's copy of a.ranges (grid sizes come from it)
 hipError_t rt_launch_build_prep(const RtBuildArgs& a, const rt_blas_range* h_ranges, hipStream_t s);        // prims, order[0], level 0
+hipError_t rt_launch_tlas_prep(const RtBuildArgs& a, hipStream_t s);         // rt_tlas.hip: prims and order[0] of a.inst (build_prep calls it)
 hipError_t rt_launch_build_level(const RtBuildArgs& a, uint32_t level, uint32_t off, uint32_t cnt, hipStream_t s);   // price, scan (-> next_count), split
 hipError_t rt_launch_build_count_up(const RtBuildArgs& a, uint32_t off, uint32_t cnt, hipStream_t s);
 hipError_t rt_launch_build_rank_down(const RtBuildArgs& a, uint32_t off, uint32_t cnt, hipStream_t s);

@@ -6,6 +6,7 @@
 // append goes to a place a prefix sum names -- two builds of the same triangles leave the same bytes, in the scratch state too.
 //
 //   prep      per slot: the triangle's float32 box and centroid (RtBbPrim, 40 bytes), order[0] = identity; per range: the root.
+//             (rt_build_tlas: the slots are instances, and rt_tlas.hip makes their prims from world boxes instead.)
 //   price     per node of the level: lane p of a 32-lane group prices plane p of the 27 over every group-th triangle of the run
 //             (the prim of an iteration is one address per group: a broadcast load out of L2), the groups' sides are merged by
 //             fminf / fmaxf / +, lane p forms cost p in float64, every lane picks the first strict minimum.  A run of up to
@@ -353,10 +354,15 @@ static uint32_t build_max_slots(const rt_blas_range* h_ranges, uint32_t n) {
 }
 
 hipError_t rt_launch_build_prep(const RtBuildArgs& a, const rt_blas_range* h_ranges, hipStream_t s) {
-    const uint32_t bx = (build_max_slots(h_ranges, a.n_ranges) + 255u) / 256u;
-    for (uint32_t r0 = 0; r0 < a.n_ranges; r0 += 65535u) {
-        const uint32_t ny = a.n_ranges - r0 < 65535u ? a.n_ranges - r0 : 65535u;
-        hipLaunchKernelGGL(rtk::build_prep, dim3(bx, ny), dim3(256), 0, s, a, r0);
+    if (a.inst.models) {                                   // the instance front end (rt_tlas.hip) makes the prims of the one range
+        const hipError_t e = rt_launch_tlas_prep(a, s);
+        if (e != hipSuccess) return e;
+    } else {
+        const uint32_t bx = (build_max_slots(h_ranges, a.n_ranges) + 255u) / 256u;
+        for (uint32_t r0 = 0; r0 < a.n_ranges; r0 += 65535u) {
+            const uint32_t ny = a.n_ranges - r0 < 65535u ? a.n_ranges - r0 : 65535u;
+            hipLaunchKernelGGL(rtk::build_prep, dim3(bx, ny), dim3(256), 0, s, a, r0);
+        }
     }
     hipLaunchKernelGGL(rtk::build_root, dim3(a.n_ranges), dim3(256), 0, s, a);
     return hipGetLastError();

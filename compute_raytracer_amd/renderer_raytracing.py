@@ -191,6 +191,60 @@ class RendererRaytracing:
         abi.check(self._lib.rt_read_tri_lookup(self._ctx, first, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._ctx)
         return out
 
+    # ---- device top-level builds (rt_build_tlas / rt_build_tlas_device / rt_read_blas / rt_read_blas_lookup) ----
+    def build_top_level(self, matrices=None):
+        """The per-frame instance state -- BLAS records, BLAS lookup and the top-level tree -- made on the device: a SAH tree over
+        the instances' tight world boxes, taken from the root boxes the device holds now (after any refit() or rebuild()), where
+        scene.update(dt) builds the reference's tree over placeholder boxes that every ray enters.  `matrices`: (M, 16) float32
+        forward instance matrices, column-major, in scene.instances order; None: scene.instances.matrices(); a torch tensor on this
+        renderer's device is read there, on torch's current stream.  Afterwards scene.frame and scene.tlasNodesUsed are the
+        device's bytes, so recalculateScene() rewrites the same state.  scene.update(dt) still builds the reference's tree: call
+        build_top_level() after it, and again after anything that grows a root box (update_triangles() + refit(), rebuild()) --
+        the boxes are tight, a stale top level can lose hits.  On exact-t ties between instances the winning (instance, prim) may
+        differ from the reference tree's; t never does.  For a handful of instances the host recipe is the faster one.  Returns
+        {nodes_used, depth, leaves, max_leaf}.  Drains the frames in flight."""
+        self.recalculateScene()
+        sc = self.scene
+        roots = np.ascontiguousarray([sc.meshes[k].root_node for k in sc.instances.mesh_index], dtype=np.uint32)
+        info = abi.RtTlasInfo()
+        tail = (roots.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), roots.shape[0], sc.tlasNodesMax, ctypes.byref(info))
+        if matrices is not None and type(matrices).__module__.split(".")[0] == "torch":
+            import torch
+            m = matrices
+            if m.dtype != torch.float32 or tuple(m.shape) != (roots.shape[0], 16) or not m.is_contiguous():
+                raise ValueError("build_top_level: matrices must be a contiguous float32 (%d, 16) tensor" % roots.shape[0])
+            if m.device.type != "cuda" or m.device.index != self.device:
+                raise ValueError("build_top_level: matrices must live on cuda:%d, this renderer's device" % self.device)
+            with self._current_stream(m.device) as stream:
+                abi.check(self._lib.rt_build_tlas_device(self._ctx, ctypes.c_void_p(m.data_ptr()), *tail, stream), self._ctx)
+        else:
+            m = np.ascontiguousarray(sc.instances.matrices() if matrices is None else matrices, dtype=np.float32)
+            if m.shape != (roots.shape[0], 16):
+                raise ValueError("build_top_level: matrices must be (%d, 16), one per instance" % roots.shape[0])
+            abi.check(self._lib.rt_build_tlas(self._ctx, m.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), *tail), self._ctx)
+        n = roots.shape[0]
+        sc.frame = dict(blas=self.read_blas(0, n), blas_lookup=self.read_blas_lookup(0, n), tlas_nodes=self.read_nodes(0, sc.tlasNodesMax))
+        sc.tlasNodesUsed = int(info.nodes_used)
+        return dict(nodes_used=int(info.nodes_used), depth=int(info.depth), leaves=int(info.leaves), max_leaf=int(info.max_leaf))
+
+    def read_blas(self, first=0, n=None):
+        """(n, 20) float32: BLAS records [first, first + n) as the next frame would read them (n None: up to the last instance).  A
+        diagnostic: it waits for the frames in flight."""
+        first = int(first)
+        n = len(self.scene.instances) - first if n is None else int(n)
+        out = np.zeros((max(n, 0), 20), dtype=np.float32)
+        abi.check(self._lib.rt_read_blas(self._ctx, first, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._ctx)
+        return out
+
+    def read_blas_lookup(self, first=0, n=None):
+        """(n,) float32: BLAS lookup words [first, first + n) as the next frame would read them (n None: up to the last instance).
+        A diagnostic: it waits for the frames in flight."""
+        first = int(first)
+        n = len(self.scene.instances) - first if n is None else int(n)
+        out = np.zeros(max(n, 0), dtype=np.float32)
+        abi.check(self._lib.rt_read_blas_lookup(self._ctx, first, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._ctx)
+        return out
+
     # ---- RR:434-470 -----------------------------------------------------------------------
     def render(self):
         import time

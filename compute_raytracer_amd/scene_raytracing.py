@@ -124,7 +124,8 @@ class SceneRaytracing:
 
     def update(self, dt):  # scene-raytracing.ts:138-143
         """Spheres are static; a triangle scene turns its instances and rebuilds the per-frame buffers
-        (instance matrices, their inverses, the top-level tree), as the reference does each frame."""
+        (instance matrices, their inverses, the top-level tree), as the reference does each frame.  That tree is the reference's,
+        over placeholder boxes every ray enters: for the tight one call RendererRaytracing.build_top_level() after this."""
         if self.instances is not None and len(self.instances):
             self.instances.turn(dt)
             self.buildTopLevel()

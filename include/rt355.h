@@ -732,6 +732,67 @@ int rt_read_tri_lookup(rt_ctx* ctx, uint32_t first_slot, uint32_t n, float* dst)
 int rt_build_blas_host(const float* triangles, uint32_t n_triangles, float* tri_lookup, uint32_t n_tri_lookup,
                        float* nodes, uint32_t n_nodes, const rt_blas_range* ranges, uint32_t n, uint32_t* used);
 
+/* ---- device top-level builds: a SAH tree over the instances' tight world boxes ------------------------------------------------------ */
+
+typedef struct rt_tlas_info {
+    uint32_t nodes_used;  /* nodes of the tree                        */
+    uint32_t depth;       /* levels below the root                    */
+    uint32_t leaves;
+    uint32_t max_leaf;    /* most instances in one leaf               */
+} rt_tlas_info;
+
+/* rt_build_tlas: the whole per-frame instance state -- BLAS records, BLAS lookup, top-level nodes -- made on the device from the
+ * instances' FORWARD matrices and the boxes the device holds at their roots.  models: n x 16 floats, column-major; roots: the root
+ * node index of each instance's bottom-level tree; nodes [0, node_cap) of the node buffer are the top level's.
+ *   BLAS record i = {invert(models[i]), (float)roots[i], 0, 0, 0}, in the caller's instance order (rt_write_instance_masks tables
+ *     and rt_hit.instance keep their meaning).  invert is gl-matrix's mat4.invert: float64 minors and cofactors of the float32
+ *     entries, each times 1 / det, one rounding to float32; det == 0: the identity.
+ *   World box of instance i: the eight corners of the node record at roots[i] (min.xyz, max.xyz as the device holds them NOW, so
+ *     after any refit or rebuild) through models[i] as vec3.transformMat4 does it (float64 products and sums left to right,
+ *     w || 1, the division, one rounding to float32), min / max from -+1e30; then padded: with m the largest absolute value of the
+ *     six bounds and pad = m * 2^-16 (float32), lo - pad and hi + pad.  Centroid (lo + hi) * 0.5f of the padded bounds.
+ *   Tree: rt_build_blas' SAH rules over these boxes (27 planes, first strict minimum, the leaf rule, a stable partition, the
+ *     children of the split of preorder rank k at 1 + 2k); the root is node 0, a leaf's word 3 is a position in the BLAS lookup,
+ *     whose words are the instance indices in leaf order.  Nodes [nodes_used, node_cap) are zero records.
+ * On success the context is in exactly the state the same bytes passed to rt_write_blas, rt_write_blas_lookup and
+ * rt_write_nodes(ctx, 0, ..., node_cap) leave it in (up to sixteen instances travel with the frames, as after those calls).
+ * Synchronous, and a scene-setup call: waits for the frames in flight.  *info (may be NULL) describes the tree.
+ * Checks, in this order, nothing changed by any of them: a NULL context, models or roots (or models_dev not 16-byte aligned):
+ * RT_ERR_INVALID_ARG; no triangle scene (no nodes written): RT_ERR_STATE; n == 0, n > 2^20, node_cap beyond the nodes written, a
+ * root at or beyond the nodes written or below node_cap: RT_ERR_INVALID_ARG; a tree of more than node_cap nodes: RT_ERR_CAPACITY
+ * -- info->nodes_used is the need, 2n - 1 always suffice --; a tree deeper than 20 levels: RT_ERR_UNSUPPORTED (the kernels keep
+ * twenty stack slots, and walking the nearer child first needs one per level); *info is set in both.  Non-finite matrix entries
+ * or boxes: the call ends and is memory-safe; no shape is promised.
+ *
+ * TWO THINGS DIFFER from the top level the reference's recipe makes (placeholder boxes of -+999999 per mesh, which cover every
+ * ray): (1) these boxes are tight, so after anything that GROWS a root box -- rt_update_triangles + rt_refit_blas, rt_build_blas,
+ * a node write -- the top level must be built again, or hits can be lost; (2) where two instances are hit at exactly the same t,
+ * the winning (instance, prim) may differ from the placeholder tree's, since the instances are visited in another order.  t never
+ * differs.
+ * Cost: one device-to-host word per level of the tree plus the read-back of the result (148 bytes per instance); for a handful of
+ * instances the host recipe is faster (DESIGN.md 4.7i has the figures) -- this call is for scenes of many instances, and for boxes
+ * that exist only on the device.
+ *
+ * rt_build_tlas_device: the same with the matrices in DEVICE memory (16-byte aligned), produced on `hip_stream` (NULL: the
+ * context's stream); the call waits for that stream.  roots and info stay host memory. */
+int rt_build_tlas(rt_ctx* ctx, const float* models /* host [n][16] */, const uint32_t* roots /* host [n] */, uint32_t n,
+                  uint32_t node_cap, rt_tlas_info* info /* may be NULL */);
+int rt_build_tlas_device(rt_ctx* ctx, const float* models_dev, const uint32_t* roots, uint32_t n, uint32_t node_cap,
+                         rt_tlas_info* info, void* hip_stream);
+
+/* Runs rt_build_tlas' algorithm on caller arrays, serially, with no device and no context: the same inline arithmetic as the
+ * kernels (csrc/rt_tlas_build.h), the same checks and results.  nodes: the node buffer the roots index, n_nodes records of 8
+ * floats.  Out: tlas_nodes [node_cap][8] (zero records behind the tree), blas [n][20], blas_lookup [n]; written only on RT_OK.  A
+ * NULL array: RT_ERR_INVALID_ARG. */
+int rt_build_tlas_host(const float* models, const uint32_t* roots, uint32_t n, const float* nodes, uint32_t n_nodes,
+                       float* tlas_nodes, float* blas, float* blas_lookup, uint32_t node_cap, rt_tlas_info* info);
+
+/* Diagnostics: rt_read_nodes for the BLAS records (20 f32 each) and the BLAS lookup words -- what the next frame would read, the
+ * copies that travel with the frames included.  Wait for the frames in flight.  first + n beyond what was written:
+ * RT_ERR_INVALID_ARG. */
+int rt_read_blas(rt_ctx* ctx, uint32_t first, uint32_t n, float* dst);
+int rt_read_blas_lookup(rt_ctx* ctx, uint32_t first, uint32_t n, float* dst);
+
 /* Which filter forms a frame of this scene may use (no device needed): *filter_ok = 0 when
  * max(|center| + |radius| over the spheres, |cameraPos|, |lightPosition|) is NaN, infinite or
  * >= 2^20 -- fast mode then renders the frame with the literal kernel --, *signed_filter = 1 when
