@@ -51,6 +51,7 @@ SYMBOLS = [
     "rt_build_blas", "rt_read_tri_lookup", "rt_build_blas_host",
     "rt_write_instance_masks", "rt_set_query_masks",
     "rt_build_tlas", "rt_build_tlas_device", "rt_build_tlas_host", "rt_read_blas", "rt_read_blas_lookup",
+    "rt_closest_points", "rt_closest_points_host", "rt_closest_points_model",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -80,6 +81,18 @@ class RtHit(ctypes.Structure):
 
 # the same record as a numpy dtype: an (n,) array of it is what rt_trace_rays_host / rt_pick fill
 HIT_DTYPE = [("t", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("instance", "<i4"), ("normal", "<f4", (3,))]
+
+
+class RtClosest(ctypes.Structure):
+    """rt_closest (include/rt355.h): the nearest surface point to one point, 32 bytes."""
+    _fields_ = [
+        ("dist2", ctypes.c_float), ("u", ctypes.c_float), ("v", ctypes.c_float),
+        ("prim", ctypes.c_int32), ("instance", ctypes.c_int32), ("point", ctypes.c_float * 3),
+    ]
+
+
+# the same record as a numpy dtype: an (n,) array of it is what rt_closest_points_host / rt_closest_points_model fill
+CLOSEST_DTYPE = [("dist2", "<f4"), ("u", "<f4"), ("v", "<f4"), ("prim", "<i4"), ("instance", "<i4"), ("point", "<f4", (3,))]
 
 
 class RtShade(ctypes.Structure):
@@ -251,6 +264,10 @@ def load():
         "rt_build_tlas_host": (ctypes.c_int, [fp, ctypes.POINTER(u32), u32, fp, u32, fp, fp, fp, u32, ctypes.POINTER(RtTlasInfo)]),
         "rt_read_blas": (ctypes.c_int, [vp, u32, u32, fp]),
         "rt_read_blas_lookup": (ctypes.c_int, [vp, u32, u32, fp]),
+        "rt_closest_points": (ctypes.c_int, [vp, vp, u32, vp, vp]),
+        "rt_closest_points_host": (ctypes.c_int, [vp, vp, u32, vp]),
+        "rt_closest_points_model": (ctypes.c_int, [vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp,
+                                                   ctypes.POINTER(ctypes.c_uint64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -22,6 +22,7 @@
 #include "rt_build.h"
 #include "rt_tlas_build.h"
 #include "rt_tlas_fit.h"
+#include "rt_closest.h"
 
 thread_local std::string g_rt_err;
 thread_local int g_rt_kernel_id = 0;
@@ -2234,6 +2235,72 @@ int rt_pick(rt_ctx* c, const uint32_t* xy, uint32_t n, rt_hit* hits) {
         RT_HIP(rt_launch_pick_rays(fa, static_cast<const uint32_t*>(c->d_qxy.p), static_cast<float4*>(c->d_qrays.p), n, q.s));
         return query_launch(c, static_cast<const float4*>(c->d_qrays.p), r[0].dev, n, q);
     });
+}
+
+// ---- closest-point queries (rt_closest.hip) --------------------------------------------------------------------------------------
+
+static_assert(sizeof(rt_closest) == 32, "rt_closest is two float4");
+
+extern "C++" { RtClosestLaunch rt_closest_launch = nullptr; }      // set by rt_closest.o (rt_tri_types.h)
+
+// The checks of both forms, in the header's order: the context, n == 0 (*done), the buffers (device: 16-byte aligned), the scene
+// written, a triangle scene
+static int closest_check(const char* who, rt_ctx* c, const float* points, uint32_t n, const rt_closest* out, bool device, bool& done) {
+    char msg[160];
+    done = false;
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (n == 0) { done = true; return RT_OK; }
+    if (!points || !out) { std::snprintf(msg, sizeof msg, "%s: NULL argument", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (device && (reinterpret_cast<uintptr_t>(points) % 16u || reinterpret_cast<uintptr_t>(out) % 16u)) {
+        std::snprintf(msg, sizeof msg, "%s: points and out must be 16-byte aligned", who);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    { int rc = query_scene_written(c, who); if (rc != RT_OK) return rc; }
+    if (c->scene_kind != 1) {
+        std::snprintf(msg, sizeof msg, "%s: sphere scenes have no closest-point query (a sphere's distance needs a square root)", who);
+        return fail(RT_ERR_UNSUPPORTED, msg);
+    }
+    return RT_OK;
+}
+
+// the per-instance constants (remade by every call, on its stream: queries run in call order), then the search
+static int closest_launch(rt_ctx* c, const float4* points, float4* out, uint32_t n, const Query& q) {
+    const size_t need = (size_t)q.ts.n_blas * kCpInstWords * 4u;
+    if (need > c->d_closest.cap) {
+        if (c->query_pending) RT_HIP(hipEventSynchronize(c->ev_query));      // an earlier call may still read the old one
+        RT_HIP(c->d_closest.replace(std::max(need, (size_t)4096u)));
+    }
+    if (!rt_closest_launch) return fail(RT_ERR_UNSUPPORTED, "rt_closest_points: this build holds no closest-point kernels (rt_closest.o is not linked)");
+    RT_HIP(rt_closest_launch(q.ts, q.inst, c->d_closest.as<float>(), points, out, n, q.s));
+    return RT_OK;
+}
+
+int rt_closest_points(rt_ctx* c, const float* points, uint32_t n, rt_closest* out, void* hip_stream) {
+    bool done;
+    { int rc = closest_check("rt_closest_points", c, points, n, out, true, done); if (rc != RT_OK || done) return rc; }
+    return query_run(c, "rt_closest_points", hip_stream, [&](const Query& q) {
+        return closest_launch(c, reinterpret_cast<const float4*>(points), reinterpret_cast<float4*>(out), n, q);
+    });
+}
+
+int rt_closest_points_host(rt_ctx* c, const float* points, uint32_t n, rt_closest* out) {
+    bool done;
+    { int rc = closest_check("rt_closest_points_host", c, points, n, out, false, done); if (rc != RT_OK || done) return rc; }
+    Staged r[] = {{out, &c->d_qhits, (size_t)n * 32u}};
+    return query_run_host(c, "rt_closest_points_host", points, &c->d_qrays, (size_t)n * 16u, r, [&](const Query& q) {
+        return closest_launch(c, static_cast<const float4*>(c->d_qrays.p), reinterpret_cast<float4*>(r[0].dev), n, q);
+    });
+}
+
+int rt_closest_points_model(const float* points, uint32_t n, const float* triangles, uint32_t n_triangles, const float* tri_lookup,
+                            uint32_t n_tri_lookup, const float* nodes, uint32_t n_nodes, const float* blas, uint32_t n_blas,
+                            const float* blas_lookup, uint32_t n_blas_lookup, const uint32_t* masks, uint32_t n_masks, uint32_t ray_mask,
+                            rt_closest* out, uint64_t* tests) {
+    const char* why = "";
+    const int rc = rt_cp_model(points, n, triangles, n_triangles, tri_lookup, n_tri_lookup, nodes, n_nodes, blas, n_blas, blas_lookup,
+                               n_blas_lookup, masks, n_masks, ray_mask, out, tests, &why);
+    if (rc != RT_OK) { char msg[200]; std::snprintf(msg, sizeof msg, "rt_closest_points_model: %s", why); return fail(rc, msg); }
+    return RT_OK;
 }
 
 // ---- shaded ray queries (rt_shade.hip) -----------------------------------------------------------------------------------------

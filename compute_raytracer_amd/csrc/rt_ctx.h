@@ -165,6 +165,7 @@ struct rt_ctx {
     // Ray queries (rt_trace_rays_host / rt_pick): query_stream, staging buffers that grow as needed, and ev_query behind the
     // latest query on any stream -- scene writes wait for it as they wait for the frames in flight (rt_drain)
     DevBuf d_qrays, d_qhits, d_qxy;
+    DevBuf d_closest;                    // closest-point queries: 16 words per BLAS record, remade by every call on its stream (rt_closest.hip: closest_inst)
     bool query_pending = false;
     bool query_versions = false;         // ... and that query (or one before it since the last drain) read a version of the per-frame buffers
     hipStream_t query_last = nullptr;    // the stream of that query

@@ -114,4 +114,12 @@ hipError_t rt_launch_gbuffer_spheres(const RtFrameArgs& a, const float* records,
 // the primary ray's hit point are occluded.  `a` and inst as for the geometry frames.
 hipError_t rt_launch_ao_triangles(const RtFrameArgs& a, const RtTriScene& t, int inst, const RtAoOut& o, hipStream_t s);
 hipError_t rt_launch_ao_spheres(const RtFrameArgs& a, const float* records, uint32_t n_spheres, const RtAoOut& o, hipStream_t s);
+// Closest-point queries (rt_closest.hip; include/rt355.h: rt_closest_points): points [n] float4 {x, y, z, radius}, out [n][2] float4
+// (rt_closest).  cst: 16 words per BLAS record of t, written by a kernel of the launch in front of the search.  inst as above.
+hipError_t rt_launch_closest_points(const RtTriScene& t, int inst, float* cst, const float4* points, float4* out, uint32_t n, hipStream_t s);
+// rt_api.hip reaches that launch through this pointer, which rt_closest.o sets while the library is loaded (null until then): rt_api.o
+// names no symbol of rt_closest.o, so a host-only program that links rt_api.o for the frame path alone (tests/c/enqueue_trace.cpp)
+// needs no stand-in for a launch no frame makes.  A null pointer at a call is an error, never a silent miss.
+typedef hipError_t (*RtClosestLaunch)(const RtTriScene&, int, float*, const float4*, float4*, uint32_t, hipStream_t);
+extern RtClosestLaunch rt_closest_launch;
 hipError_t rt_launch_pick_rays(const RtFrameArgs& a, const uint32_t* xy, float4* rays, uint32_t n, hipStream_t s);   // xy: [n][2] u32

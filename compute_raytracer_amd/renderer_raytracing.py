@@ -481,6 +481,58 @@ class RendererRaytracing:
                 abi.check(self._lib.rt_trace_rays(*args, *tail), self._ctx)
         return out
 
+    # ---- closest-point queries: the nearest surface point to the host's points (rt_closest_points / rt_closest_points_host) -----
+    def closest_points(self, points, radius=float("inf"), out=None):
+        """The nearest point of the scene's surface to each point, within `radius`, against the scene the next frame would render
+        (recalculateScene() first, as render() does).  Triangle scenes only; instances hidden from the nearest-hit ray mask
+        (set_query_masks) are left out.
+
+        numpy: points (n, 3), radius a scalar or an (n,) array -> dict of arrays dist2, dist (the square root of dist2, taken here
+        on the host; -1 on a miss), u, v, prim, instance (n,), point (n, 3) and mesh (the instance's mesh index, -1 on a miss),
+        through rt_closest_points_host.  A miss has dist2 = -1 and prim = instance = -1.
+        torch: `points` is a float32 (n, 4) tensor {x, y, z, radius} on this renderer's device (`radius` must stay at its default)
+        -> an (n, 8) float32 tensor of rt_closest records (prim / instance as int32 bits: .view(torch.int32)), or `out`, enqueued
+        through rt_closest_points on torch.cuda.current_stream()."""
+        if type(points).__module__.split(".")[0] == "torch":
+            import torch
+            if not (isinstance(radius, float) and radius == float("inf")):
+                raise ValueError("closest_points: with a tensor the radius is word 3 of each point")
+            if points.dtype != torch.float32 or points.dim() != 2 or points.shape[1] != 4 or not points.is_contiguous():
+                raise ValueError("closest_points: points must be a contiguous float32 (n, 4) tensor")
+            if points.device.type != "cuda" or points.device.index != self.device:
+                raise ValueError("closest_points: points must live on cuda:%d, this renderer's device" % self.device)
+            if out is None:
+                out = torch.empty((points.shape[0], 8), dtype=torch.float32, device=points.device)
+            elif out.element_size() != 4 or tuple(out.shape) != (points.shape[0], 8) or not out.is_contiguous() or out.device != points.device:
+                raise ValueError("closest_points: out must be a contiguous 32-bit (n, 8) tensor on the points' device")
+            self.recalculateScene()
+            with self._current_stream(points.device) as stream:
+                abi.check(self._lib.rt_closest_points(self._ctx, ctypes.c_void_p(points.data_ptr()), points.shape[0],
+                                                      ctypes.c_void_p(out.data_ptr()), stream), self._ctx)
+            return out
+        if out is not None:
+            raise ValueError("closest_points: out= is for (n, 4) tensors")
+        p = np.asarray(points, dtype=np.float32).reshape(-1, 3)
+        rad = np.asarray(radius, dtype=np.float32)
+        if rad.ndim > 1 or (rad.ndim == 1 and rad.shape[0] != p.shape[0]):
+            raise ValueError("closest_points: radius is a scalar or an (n,) array")
+        pts = np.zeros((p.shape[0], 4), dtype=np.float32)
+        pts[:, 0:3] = p
+        pts[:, 3] = rad
+        self.recalculateScene()
+        rec = np.zeros(pts.shape[0], dtype=abi.CLOSEST_DTYPE)
+        abi.check(self._lib.rt_closest_points_host(self._ctx, pts.ctypes.data, pts.shape[0], rec.ctypes.data), self._ctx)
+        res = {"dist2": rec["dist2"].copy(), "u": rec["u"].copy(), "v": rec["v"].copy(), "prim": rec["prim"].copy(),
+               "instance": rec["instance"].copy(), "point": np.ascontiguousarray(rec["point"])}
+        with np.errstate(invalid="ignore"):
+            root = np.sqrt(res["dist2"])
+        res["dist"] = np.where(np.isnan(root), np.float32(-1.0), root).astype(np.float32)
+        if self.scene.hasTriangles:
+            mesh_index = np.asarray(self.scene.instances.mesh_index, dtype=np.int64)
+            inst = res["instance"]
+            res["mesh"] = np.where(inst >= 0, mesh_index[np.clip(inst, 0, len(mesh_index) - 1)], -1)
+        return res
+
     # ---- multi-hit queries: the k nearest hits of the host's rays (rt_trace_rays_multi / rt_trace_rays_multi_host) -------------
     def trace_rays_multi(self, origins, directions=None, k=4, tmin=None, tmax=None, limits=False, out=None):
         """The first k surfaces each ray crosses (1 <= k <= abi.RT355_MAX_HITS), sorted by (t, instance, prim); the conventions

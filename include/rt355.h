@@ -554,6 +554,69 @@ int rt_render_ao_host(rt_ctx* ctx, const uint32_t* rect, const float* dirs, uint
 int rt_write_instance_masks(rt_ctx* ctx, const uint32_t* masks, uint32_t n);   /* host memory */
 int rt_set_query_masks(rt_ctx* ctx, uint32_t nearest, uint32_t occlusion);
 
+/* ---- closest-point queries: the nearest surface point to points the host supplies ----------------------------------------------- */
+
+typedef struct rt_closest {
+    float dist2;      /* squared world distance to the nearest surface point; -1: nothing within the radius */
+    float u, v;       /* barycentrics of that point on the triangle: weight of corner B, of corner C (rt_hit's meaning) */
+    int32_t prim;     /* u32(triangleLookup[slot]), as rt_hit.prim; -1 */
+    int32_t instance; /* BLAS record index, as rt_hit.instance; -1 */
+    float point[3];   /* the surface point, world space; 0 */
+} rt_closest;         /* 32 bytes */
+
+/* rt_closest_points / rt_closest_points_host: for each point {x, y, z, radius} ([n][4] f32) the nearest point of the triangle scene's
+ * surface within the radius, in all directions -- the query no ray can stand in for.  Device form: `points` and `out` in device
+ * memory of this context's GPU, 16-byte aligned, enqueued on `hip_stream` (NULL = the context's stream), returns at once.  Host
+ * form: host memory, synchronous, staged through the context's query buffers.
+ *
+ * What the answer is (csrc/rt_closest.h holds every expression; it is the definition).
+ *   1. Candidates.  Every pair of an instance bi that a leaf of the top-level tree names and whose mask shares a bit with the
+ *      context's nearest-hit ray mask (rt_set_query_masks), and a triangle-lookup slot in a leaf under the root of bi's BLAS record:
+ *      the slots traceBLAS (RK:246-332) can reach.  Back faces count: nothing is culled.
+ *   2. Corners.  The object corners A, B, C are words 0-2, 12-14 and 24-26 of the triangle record.  The instance's forward matrix is
+ *      Fm = mat4.invert (rt_build_tlas' invert: float64, one rounding) of record words 0..15, a float32 result.  Component k of a world
+ *      corner is ((Fm[k] x + Fm[4+k] y) + Fm[8+k] z) + Fm[12+k] in float64, left to right, rounded once to float32.  The matrix is
+ *      treated as affine: its bottom row is not read.
+ *   3. Leaf.  The closest point of the float32 point to the float32 world triangle, in float64, by the region tests of Ericson,
+ *      Real-Time Collision Detection 5.1.5, tested in the order vertex A, vertex B, edge AB, vertex C, edge AC, edge BC, interior; every
+ *      dot product (x x' + y y') + z z', no fused multiply-add; d2 = (ex ex + ey ey) + ez ez with e = p - q.  dist2, u, v and point are
+ *      those float64 values rounded once to float32.  Nothing reported passes through a square root.
+ *   4. Acceptance.  r2 = radius * radius in float32; a candidate counts iff dist2 <= r2, compared on the rounded value.  A negative or
+ *      NaN radius gives the miss record, +inf an unbounded search.  A candidate whose dist2 is NaN (zero-area triangles, which the ray
+ *      tests never hit either) is no candidate.
+ *   5. Winner.  The smallest candidate under the total order (dist2, instance, prim).  Miss: dist2 = -1, prim = instance = -1,
+ *      everything else 0.
+ * The result therefore does not depend on the order of the walk: points on a shared edge or vertex, and coincident instances, tie
+ * exactly in dist2 and resolve by index.
+ *
+ * The walk visits both levels nearest box first and skips a box only when a lower bound of the world distance to anything in it is
+ * strictly beyond the best distance so far (so an exact tie is still visited); the bound holds under any affine instance matrix
+ * (DESIGN.md 4.7j).  It keeps 20 top-level and 32 bottom-level stack entries per point, one per level: every tree rt_build_blas,
+ * rt_build_tlas and the host builders make is searched exhaustively.  On a hand-made tree deeper than that the walk drops what its
+ * stacks cannot hold and is memory-safe; it reports only true candidates, and promises no more than that.  Tight top-level boxes
+ * (rt_build_tlas) are what make the search prune across instances; under the reference's placeholder boxes every instance is entered.
+ *
+ * Contract.  That of rt_trace_rays, word for word: sees every write made before it, per-frame instance writes that no frame has
+ * carried yet included; takes no slot of the event ring, changes no field of rt_stats, has no rt_kernel_id; is unaffected by
+ * rt_select_kernel, rt_set_mode and rt_set_variant; never disturbs frames in flight; queries run in call order, and scene writes
+ * after one wait for it.
+ *
+ * Checks, in this order: a NULL context: RT_ERR_INVALID_ARG; n == 0: RT_OK; a NULL buffer, or in the device form a misaligned one:
+ * RT_ERR_INVALID_ARG; no scene written: RT_ERR_STATE; a sphere scene: RT_ERR_UNSUPPORTED (a sphere's distance needs a square root
+ * inside the reported value) -- the context stays usable.
+ *
+ * rt_closest_points_model: the same search, serially, on caller arrays in the layouts of rt_write_* (triangles 40 floats each, nodes 8,
+ * BLAS records 20; `masks` as for rt_write_instance_masks, `ray_mask` the nearest-hit mask) -- no device and no context, the same
+ * inline arithmetic as the kernel.  *tests (may be NULL) receives the number of (instance, slot) candidates evaluated.  n == 0:
+ * RT_OK; a NULL array (masks with n_masks != 0 included): RT_ERR_INVALID_ARG; an empty array: RT_ERR_STATE. */
+int rt_closest_points(rt_ctx* ctx, const float* points /* [n][4] {x,y,z,radius} */, uint32_t n, rt_closest* out, void* hip_stream); /* device, async */
+int rt_closest_points_host(rt_ctx* ctx, const float* points, uint32_t n, rt_closest* out);                                          /* host, sync   */
+int rt_closest_points_model(const float* points, uint32_t n, const float* triangles, uint32_t n_triangles,
+                            const float* tri_lookup, uint32_t n_tri_lookup, const float* nodes, uint32_t n_nodes,
+                            const float* blas, uint32_t n_blas, const float* blas_lookup, uint32_t n_blas_lookup,
+                            const uint32_t* masks, uint32_t n_masks, uint32_t ray_mask,
+                            rt_closest* out, uint64_t* tests /* may be NULL */);
+
 /* ---- multi-GPU: render + RCCL gather behind one call (RR:434-470 across a group of GPUs) ------ */
 
 /* One process per GPU.  Rank 0 calls rt_comm_unique_id and hands the bytes to the other ranks by
