@@ -102,6 +102,34 @@
 //      the 10u); the sum t_k + dA rounds by u, inside the 16u.  The lane then counts the shadow ray (the frame's ray count is
 //      the reference's) and takes the second half of the shading block in the same trip: a lane spared only the walk would
 //      idle through it beside the wave's other lanes.
+//      t_k is not formed (shadow_decided): it enters three comparisons only, and a root and a quotient in IEEE form are some
+//      twenty instructions of every trip.  Write n = -b > 0, S = sqrt(disc), A = 2a >= 0 -- disc, b and a are the literal
+//      statements' values, the reference's bits -- so that the literal t_k = fl(fl(n - fl(S)) / A) = (n - S (1 + e1))(1 + e2)(1 + e3) / A,
+//      |e| <= u.  For a bound X > 0, t_k <= X follows from n - S (1 - u) <= A X (1 - 2.01u), t_k > X from n - S (1 + u) > A X (1 + 4u).
+//      The kernel forms w = fl(n - A B) and v = fl(n - A * 0.0010001) with one FMA each (the sign is exact, the value within u)
+//      and compares squares: w <= 0 or fl(w w) <= fl(disc (1 - 8u)), and v > 0 and fl(v v) > fl(disc (1 + 8u)).  The square and
+//      the product by (1 -+ 8u) round by u each, w and v by u: (n - A B)^2 <= disc (1 - 8u)(1 + 4.05u) <= disc (1 - u)^2, and
+//      (n - 0.001 A (1 + 4u))^2 >= v^2 (1 - 2u) > disc (1 + 8u)(1 - 4.02u) >= disc (1 + u)^2 -- the margins are relative to disc, so
+//      they scale with the half chord S / A as the roundings of the literal t_k do (a ground sphere of radius 1e4 gives up
+//      5e-3 of t_k where its literal t_k is good to 6e-4).  disc > 2^-100 instead of disc > 0 keeps disc (1 -+ 8u) a normal
+//      number; a square that overflows is +inf and compares as such (fl(v v) = inf > a finite product is true of the real
+//      numbers too).  B = fl(len (1 - 32u) - dA') in one FMA, dA' the sum above: len (1 - 16u) rounds to l_lo >= len (1 - 17.01u),
+//      so len (1 - 32u) - dA' <= (l_lo - dA') - 14.99u len, B is that within u max(len, dA'), and for l_lo - dA' > 0 (then dA' < len)
+//      B <= (l_lo - dA')(1 - 2.01u); otherwise B <= 0, and then w >= n > S by the v comparison: no yes.  So a yes gives the literal
+//      t_k <= l_lo - dA' in real numbers, hence fl(t_k + dA') <= l_lo (rounding is monotone): every yes is a yes of the literal form
+//      `t_k > 0.001f && t_k < 9999.0f && t_k + dA' <= l_lo`, to which the paragraph above applies; t_k < 9999 from B < 9998 and
+//      t_k <= B (1 + 3u).  A NaN in any operand makes v or w or disc NaN and every comparison is written to fail on one; A = inf
+//      gives v = -inf or NaN.  What is given up -- literal yeses within 32u len + 8u S / A of a bound -- walks its shadow ray.
+//  D'. A suspended shadow walk that holds a blocker is over (shadow_blocked; the kernel, after trace_bvh).  D's argument uses of k
+//      only that the reference's loop tests it and accepts it at t_k <= l - dA.  When a wave suspends the walk (TAIL), drain() has
+//      evaluated the lane's candidates with the literal statements: (t, idx) is the reference's own acceptance of sphere idx on
+//      the ray (L, s) at t, 0.001 < t < 9999.  The reference's nearest hit is then t_min <= t, and with t <= l - dA it is not at P:
+//      RK:165 returns minIntensity whatever the rest of the walk would find, so the walk ends there (node = n), t and idx stay,
+//      light_term finds the hit at t off P by the same bound and returns minIntensity.  Root-free: dl = fl(P - L) has |dl| within
+//      u of l, q = fl(dl . dl) <= l^2 (1 + 5.1u); x = fl(t + d) with d = fl(0.0050011 + 32u (|dl|_1 + |L|_1)) and fl(x x) < q give
+//      t + d <= l (1 + 4.3u), and 32u of the l1 norms (>= (l + |L|)(1 - 5u)) pays dA's 10u and the 4.3u: t <= l - dA.  Strictly
+//      less, so that an infinite square on both sides is a no like a NaN.  The lane takes block B in the same trip and is
+//      counted there, once.
 // Forward rays (lam = 0, eps_o = 0, m = 0) are steps 1-3 unchanged.
 // The argument is checked the only way that counts: frames are compared bit for bit with the
 // oracle (tests/test_bvh_gpu.py: golden frames, random scenes over five orders of magnitude), and the walk, restated in
@@ -124,9 +152,15 @@
 // with these defaults.  Round-1 kernel (tools/ab.py): C3 3.93 / 3.51 / 3.36 / 3.40 / 3.44 ms and C5 40.7 /
 // 32.5 / 29.1 / 27.8 / 27.3 ms for 0 / 8 / 16 / 24 / 32 -- the larger the scene, the longer the walk
 // relative to the shading a suspension repeats; today's kernel: C3 flat between 8 and 24, C5 best at 32
-// (profiles/r02/tail2.log, tail3.log, tail_c5.log).
+// (profiles/r02/tail2.log, tail3.log, tail_c5.log).  Swept again with claims D and D' in place (profiles/r25/tail_*.log,
+// tools/knob_ab.py): C3 in flight 12 / 14 / 16 / 18 / 20 / 24 / 28 = 1.370 / 1.356 / 1.348 / 1.343 / 1.341 / 1.348 / 1.366 ms, one frame at
+// a time 8 / 10 / 12 / 14 / 16 / 20 = 1.747 / 1.734 / 1.719 / 1.717 / 1.723 / 1.722, C5 20 / 24 / 28 / 32 / 40 = 12.22 / 11.95 / 11.80 / 11.77 /
+// 12.15 -- 20 and 32 lanes are ahead by 0.6 % and 0.3 %, less than three spreads of `bench.py --full --repeats 5`: unchanged.
 #ifndef RT_BVH_GRAB
 #define RT_BVH_GRAB 256u   /* pixel slots per cursor atomic: a multiple of 64 (whole tiles) */
+#endif
+#ifndef RT_BVH_END_SUSPENDED
+#define RT_BVH_END_SUSPENDED 1   /* end a suspended shadow walk that already holds a blocker (claim D') */
 #endif
 #ifndef RT_BVH_TAIL_SMALL
 #define RT_BVH_TAIL_SMALL 16   /* 8-wave workgroups (scenes up to ~1300 spheres), frames in flight: 12 / 14 / 16 / 18 / 20 / 24 = 1.574 / 1.565 / 1.563 / 1.565 / 1.572 / 1.598 ms (profiles/r03/tail_sweep.log; round 2, slower steps: 20) */
@@ -316,19 +350,43 @@ __device__ __forceinline__ void reversed_shadow_walk(bool shadow, v3 L, float li
 // roundings of the root and the quotient and no register beyond this block.  len = fl|P - L| as normalize() formed it (within
 // 4u of |P - L|: 16u below it is a lower bound); len + |L|_1 >= (|P - L| + |L|)(1 - 4u), and 16u of that covers claim A's 10u.
 // Every comparison is written so that a NaN anywhere answers "no".
+// t_k itself is never formed: it enters three comparisons only, and each is decided on n = -b, disc and A = 2a, the reference's
+// bits, by a product and a square (claim D of the header, second half) -- a yes here is a yes of the literal form
+//     tk = (-b - sqrtf(disc)) / (2a);   tk > 0.001f && tk < 9999.0f && tk + d_a <= len * (1 - 16u)
+// and a few literal yeses within some 30u of an edge are given up (tests/test_shadow_compare_cpu.py counts them): such a lane
+// walks its shadow ray.
 #define RT_BVH_DEC_DELTA 0.0050011f                 /* >= 0.005001 of claim A, and the rounding of the sum it enters */
 #define RT_BVH_DEC_REL 9.5367431640625e-07f         /* 2^-20 = 16u */
+#define RT_BVH_CMP_REL 1.9073486328125e-06f         /* 2^-19 = 32u: the 16u above, and 16u for the bound's own rounding and t_k's */
+#define RT_BVH_CMP_DISC 4.76837158203125e-07f       /* 2^-21 = 8u on disc: the root's rounding, and the square's it is compared with */
+#define RT_BVH_CMP_TMIN 0.0010001f                  /* > 0.001 (1 + 8u) */
+#define RT_BVH_CMP_TMAX 9998.0f                     /* t_k <= B (1 + 3u) < 9999 */
+#define RT_BVH_CMP_DISC_MIN 7.888609052210118e-31f  /* 2^-100: disc (1 +- 8u) is then a normal number */
 __device__ __forceinline__ bool shadow_decided(v3 L, float light_l1, v3 s, float len, v3 c, float r2) {
     const float a2 = dot(s, s);                           // HK:308
     const v3 oc = sub(L, c);
     const float b = 2.0f * dot(s, oc);                    // HK:309
     const float cc = dot(oc, oc) - r2;                    // HK:310
     const float disc = b * b - (4.0f * a2) * cc;          // HK:311
-    if (!(disc > 0.0f && b < 0.0f)) return false;         // HK:316
-    const float tk = (-b - sqrtf(disc)) / (2.0f * a2);    // HK:317
+    const float A = 2.0f * a2, nb = -b;                   // HK:317: t_k = (nb - sqrt(disc)) / A
     const float d_a = __builtin_fmaf(len + light_l1, RT_BVH_DEC_REL, RT_BVH_DEC_DELTA);
-    const float l_lo = len * (1.0f - RT_BVH_DEC_REL);
-    return tk > 0.001f && tk < 9999.0f && tk + d_a <= l_lo;   // HK:318, and claim D
+    const float B = __builtin_fmaf(len, 1.0f - RT_BVH_CMP_REL, -d_a);      // <= (len (1 - 16u) - d_a)(1 - 2.01u), or <= 0
+    const float v = __builtin_fmaf(-A, RT_BVH_CMP_TMIN, nb);              // t_k > 0.001:  nb - 0.001 A > sqrt(disc)
+    const float w = __builtin_fmaf(-A, B, nb);                            // t_k <= B:     nb - A B <= sqrt(disc)
+    const bool accepted = disc > RT_BVH_CMP_DISC_MIN && b < 0.0f;         // HK:316
+    const bool above = v > 0.0f && v * v > disc * (1.0f + RT_BVH_CMP_DISC);
+    const bool below = B < RT_BVH_CMP_TMAX && (w <= 0.0f || w * w <= disc * (1.0f - RT_BVH_CMP_DISC));
+    return accepted && above && below;                    // HK:318, and claim D
+}
+
+// Claim D' of the header: a shadow ray whose walk is suspended and whose literal minimum so far, t (> 0.001, of the pooled
+// evaluation: the reference's bits), ends short of the shaded point P by claim A's margin is settled -- the reference's
+// nearest hit is no later.  Root-free: (t + d)^2 < fl|P - L|^2 with d = 0.0050011 + 32u (|P - L|_1 + |L|_1).
+__device__ __forceinline__ bool shadow_blocked(v3 L, float light_l1, v3 P, float t) {
+    const v3 dl = sub(P, L);
+    const float l1 = (__builtin_fabsf(dl.x) + __builtin_fabsf(dl.y)) + __builtin_fabsf(dl.z);
+    const float x = t + __builtin_fmaf(l1 + light_l1, RT_BVH_CMP_REL, RT_BVH_DEC_DELTA);
+    return x * x < dot(dl, dl);      // (strictly: infinite on both sides is a no, like a NaN)
 }
 
 // Advances the walk of every lane's ray (o, d).  R/L: node records and links (LDS or global),
@@ -544,7 +602,7 @@ __device__ __forceinline__ void trace_bvh(const uint32_t tail, const float4* __r
             const bool pass = passes(g);
             const bool leaf = (int)lk < 0;
 #ifdef RT_BVH_COUNT
-            if (RT_BVH_COUNT == 2) g_steps += j != jn ? 1u : 0u;
+            if (RT_BVH_COUNT == 2 || RT_BVH_COUNT == 18) g_steps += j != jn ? 1u : 0u;
             if (RT_BVH_COUNT == 6) g_steps += leaf ? 1u : 0u;                              // leaf tests (lane)
             if (RT_BVH_COUNT == 7) g_steps += (!leaf && pass) ? 1u : 0u;                   // inner nodes passed (lane)
             if (RT_BVH_COUNT == 8) g_steps += (!leaf && lk != j) ? 1u : 0u;                // inner nodes tested (lane; the sentinel links to itself)
@@ -661,6 +719,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
     v3 normal = V(0, 0, 1), sdir = V(0, 0, 1), albedo = V(0, 0, 0);
     float dist = 0.0f, affect = 1.0f, sum = 0.0f, distance = 1.0f;
     uint32_t node = n;           // position of the lane's current ray in the node array; n: none
+#ifdef RT_BVH_COUNT
+    bool doomed = false;         // (modes 17, 18) the lane's shadow walk could have been ended at a suspension
+#endif
     float t = 9999.0f;           // nearest hit of the current ray so far (RK:172)
     int idx = -1;
 
@@ -738,10 +799,21 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
         else if (shadow) wo = sc.lightPos;
 #ifdef RT_BVH_COUNT
         if (RT_BVH_COUNT == 3) nrays += lane == 0u ? 1u : 0u;                          // outer iterations (wave)
-        trace_bvh<SGN, NLDS, CAP, WAVES == 16>(A.bvh_tail, R, L, n, A.geo, slot, best, node, shadow ? sc.lightPos : ro, shadow ? sdir : rd, wo, wd, madd, t, idx, nrays);
+        uint32_t walk_acc = 0u;
+        trace_bvh<SGN, NLDS, CAP, WAVES == 16>(A.bvh_tail, R, L, n, A.geo, slot, best, node, shadow ? sc.lightPos : ro, shadow ? sdir : rd, wo, wd, madd, t, idx, walk_acc);
+        nrays += (RT_BVH_COUNT != 18 || doomed) ? walk_acc : 0u;                       // 18: lane-steps of shadow walks after the suspension that could have ended them
+        // 17, 18 leave the walk alone and count what ending it would have ended
+        if (shadow && node != n && idx >= 0 && !doomed && shadow_blocked(sc.lightPos, light_l1, ro, t)) {
+            if (RT_BVH_COUNT == 17) nrays += 1u;                                       // shadow walks a suspension could have ended (lane)
+            if (RT_BVH_COUNT == 17 || RT_BVH_COUNT == 18) doomed = true; else if (RT_BVH_END_SUSPENDED) node = n;
+        }
         if (walking && node == n) {
+            doomed = false;
 #else
         trace_bvh<SGN, NLDS, CAP, WAVES == 16>(A.bvh_tail, R, L, n, A.geo, slot, best, node, shadow ? sc.lightPos : ro, shadow ? sdir : rd, wo, wd, madd, t, idx);
+        // A suspended shadow walk that already holds a blocker is over (claim D' of the header): t and idx stay, light_term finds
+        // the hit away from P.  The lane takes block B below in this trip, like any completed shadow ray, and is counted there.
+        if (RT_BVH_END_SUSPENDED && shadow && node != n && idx >= 0 && shadow_blocked(sc.lightPos, light_l1, ro, t)) node = n;
         if (walking && node == n) {                                      // this lane's ray is complete
             ++nrays;
 #endif
