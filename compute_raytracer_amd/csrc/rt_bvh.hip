@@ -635,6 +635,9 @@ inline bool lds_fits(size_t k, size_t bytes) { return k * ((bytes + 1279u) / 128
 // chain of dependent LDS reads, and the extra waves hide it (3.93 vs 4.40 ms at C3); 16-wave
 // workgroups serve scenes whose nodes leave room for one workgroup per CU only (4 waves per SIMD).
 // FLAT: compiled for a one-colour 1x1 sky (A.sky_flat; C1-C4) -- no cube filtering code in the kernel.
+// Primary directions are made once per 8x8 tile, slot l in lane l, by all 64 lanes (tile_dir), and handed to the idle lanes
+// that take the tile's pixels: primary_dir -- two IEEE divisions by W, a root and three more divisions, ~95 VALU
+// instructions -- used to run in every trip of the outer loop for the ten or so lanes that had just finished a path.
 template <int WAVES, bool SGN, bool NLDS, int CAP, bool FLAT>
 __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(const RtFrameArgs A) {
     extern __shared__ float4 lds[];
@@ -691,10 +694,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
                   __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(c.y))),
                   __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(c.z))));
     }
-    auto flat_sky = [&](v3 r) -> v3 {
-        const float z = (r.x * 0.0f + r.y * 0.0f) + r.z * 0.0f;
-        return V(sky_c.x + z, sky_c.y + z, sky_c.z + z);
-    };
+    // ... in two halves.  z is all of a sample that depends on the direction, and it is +-0 or NaN: c + (+-0) is c (a texel is
+    // never -0), and a NaN sample makes the composed pixel NaN in every channel whatever its payload (compose_pixel_sky; unorm8
+    // stores 0 for it).  So the fog colour of a pixel -- the sample along its PRIMARY direction, needed when the path ends -- is
+    // carried as one bit per lane (fog_nan: a lane mask in scalar registers) instead of three floats.
+    auto flat_z = [](v3 r) -> float { return (r.x * 0.0f + r.y * 0.0f) + r.z * 0.0f; };
+    auto flat_sky = [&](float z) -> v3 { return V(sky_c.x + z, sky_c.y + z, sky_c.z + z); };
     const float light_l1 = (__builtin_fabsf(sc.lightPos.x) + __builtin_fabsf(sc.lightPos.y)) + __builtin_fabsf(sc.lightPos.z);
     const uint32_t tiles_x = (A.W + 7u) / 8u;
     const uint32_t total = A.n_local_tiles * tiles_x * 64u;      // pixel slots, tile-major
@@ -707,6 +712,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
     const uint32_t plenty = gridDim.x * (uint32_t)WAVES * 64u * 16u;  // sixteen tiles per resident wave
     uint32_t grab = 64u, trips = 0u;                                  // wave-uniform
     bool exhausted = false;
+    // primary_dir of pixel slot `lane` of the tile the cursor is in (slots outside the frame hold whatever the arithmetic
+    // gives: they are never handed out).  A tile lasts a wave about six trips: these three registers live across walks.
+    v3 tile_dir = V(0, 0, 1);
 #ifdef RT_BVH_COUNT
     const uint64_t clk0 = wall_clock64();      // 100 MHz
     uint64_t clk_x = 0;                        // when this wave found the cursor exhausted
@@ -714,10 +722,13 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
 
     // per-lane path state (RK:101-144 unrolled into a state machine)
     bool active = false, shadow = false;
-    uint32_t opix = 0, bounce = 0, nrays = 0;
-    v3 ro = V(0, 0, 0), rd = V(0, 0, 1), color = V(1, 1, 1), fog = V(0, 0, 0);
+    uint32_t opix = 0, bounce = 0;
+    // rays are counted per WAVE (ballots taken where the wave is whole: a scalar register), per lane only in the counting builds
+    uint32_t nrays = 0;
+    v3 ro = V(0, 0, 0), rd = V(0, 0, 1), color = V(1, 1, 1);
+    bool fog_nan = false;        // FLAT: flat_z of the pixel's primary direction is NaN
     v3 normal = V(0, 0, 1), sdir = V(0, 0, 1), albedo = V(0, 0, 0);
-    float dist = 0.0f, affect = 1.0f, sum = 0.0f, distance = 1.0f;
+    float dist = 0.0f, affect = 1.0f, sum = 0.0f;
     uint32_t node = n;           // position of the lane's current ray in the node array; n: none
 #ifdef RT_BVH_COUNT
     bool doomed = false;         // (modes 17, 18) the lane's shadow walk could have been ended at a suspension
@@ -762,26 +773,37 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
                 chunk_first = cur;
                 chunk_ty = (cur >> 6) / tiles_x;
                 chunk_tx = (cur >> 6) - chunk_ty * tiles_x;
+                tile_dir = primary_dir(A, sc, chunk_tx * 8u + (lane & 7u), (A.tile_first + chunk_ty * A.tile_step) * 8u + (lane >> 3));
+#ifdef RT_BVH_COUNT
+                if (RT_BVH_COUNT == 20) nrays += lane == 0u ? 1u : 0u;                                  // tile generations (wave)
+#endif
             }
+#ifdef RT_BVH_COUNT
+            if (RT_BVH_COUNT == 19) nrays += lane == 0u ? 1u : 0u;                                      // executions of the hand-out block (wave)
+#endif
             const uint32_t tile_end = min(end, (cur & ~63u) + 64u);
             const uint32_t take = min((uint32_t)__popcll(idle), tile_end - cur);
             const uint32_t r = (uint32_t)__popcll(idle & ((1ull << lane) - 1ull));
-            if (!active && r < take) {
-                const uint32_t l = (cur + r) & 63u;
-                const uint32_t ty = chunk_ty, tx = chunk_tx;
-                const uint32_t x = tx * 8u + (l & 7u), row = l >> 3;
-                const uint32_t y = (A.tile_first + ty * A.tile_step) * 8u + row;
-                if (x < A.W && y < A.H) {                        // RR:445: outside the texture: nothing
-                    opix = (ty * 8u + row) * A.W + x;
-                    ro = sc.cameraPos; rd = primary_dir(A, sc, x, y);
-                    if (FLAT && sc.bounces == 0u) fog = scale(sc.minIntensity, flat_sky(rd));   // no ray will be cast
-                    color = V(1.0f, 1.0f, 1.0f); dist = 0.0f;    // RK:102-103
-                    affect = 1.0f; sum = 0.0f; bounce = 0u;      // RK:106-107
-                    shadow = false;
-                    active = true;
-                    node = 0u; t = 9999.0f; idx = -1;            // primary ray
-                    if (sc.bounces == 0u) node = n;              // RK:113: the loop body never runs
-                }
+            const uint32_t l = (cur + r) & 63u;
+            // every lane reads (a bpermute returns 0 for a source lane that is switched off), the takers keep what they read
+            const int la = (int)(l << 2);
+            const v3 dir = V(__int_as_float(__builtin_amdgcn_ds_bpermute(la, __float_as_int(tile_dir.x))),
+                             __int_as_float(__builtin_amdgcn_ds_bpermute(la, __float_as_int(tile_dir.y))),
+                             __int_as_float(__builtin_amdgcn_ds_bpermute(la, __float_as_int(tile_dir.z))));
+            const uint32_t ty = chunk_ty, tx = chunk_tx;
+            const uint32_t x = tx * 8u + (l & 7u), row = l >> 3;
+            const uint32_t y = (A.tile_first + ty * A.tile_step) * 8u + row;
+            // one condition, one branch: every level of a nest costs each lane mask that lives across it three scalar instructions
+            if ((!active) & (r < take) & (x < A.W) & (y < A.H)) {    // RR:445: outside the texture: nothing
+                opix = (ty * 8u + row) * A.W + x;
+                ro = sc.cameraPos; rd = dir;                     // = primary_dir(A, sc, x, y): the same statements on the same values
+                if (FLAT && sc.bounces == 0u) { const float z = flat_z(rd); fog_nan = z != z; }   // no ray will be cast
+                color = V(1.0f, 1.0f, 1.0f); dist = 0.0f;        // RK:102-103
+                affect = 1.0f; sum = 0.0f; bounce = 0u;          // RK:106-107
+                shadow = false;
+                active = true;
+                node = 0u; t = 9999.0f; idx = -1;                // primary ray
+                if (sc.bounces == 0u) node = n;                  // RK:113: the loop body never runs
             }
             cur += take;
             idle = __ballot(!active);
@@ -790,6 +812,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
 
         bool finished = active && sc.bounces == 0u;
         bool missed = false;
+        bool decided = false;        // (claim D) the lane's shadow ray was settled in this trip without a walk
         const bool walking = node != n;
         // the ray the walk selects candidates with (recomputed per trip from the path state: a suspended walk resumes
         // with the same values)
@@ -814,15 +837,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
         // A suspended shadow walk that already holds a blocker is over (claim D' of the header): t and idx stay, light_term finds
         // the hit away from P.  The lane takes block B below in this trip, like any completed shadow ray, and is counted there.
         if (RT_BVH_END_SUSPENDED && shadow && node != n && idx >= 0 && shadow_blocked(sc.lightPos, light_l1, ro, t)) node = n;
+        nrays += (uint32_t)__popcll(__ballot(walking && node == n));
         if (walking && node == n) {                                      // this lane's ray is complete
-            ++nrays;
 #endif
             const float next = affect + sum;                             // RK:120
             // The two halves run one after the other, not either / or: A for the lanes whose reflection ray is complete, then
             // B for the lanes whose shadow ray is complete AND for those whose shadow ray A has just settled without a walk
             // (claim D of the header) -- such a lane starts its next reflection ray in this very trip.
             const bool shadow_done = shadow;
-            bool decided = false;
             if (!shadow) {
                 // The centre and colour of the sphere a reflection ray has hit are requested HERE, by hand, and awaited
                 // where they are used: a wave issues in order, and the miss branch of the other lanes (three IEEE divisions)
@@ -842,8 +864,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
                 // the pixel = the sky along the PRIMARY direction, which is rd at bounce 0).
                 // A textured sky (!FLAT) is not sampled here at all: the lane leaves a record, sky_resolve does it.
                 v3 sky = V(0, 0, 0);
-                if (FLAT && (bounce == 0u || idx < 0)) sky = scale(sc.minIntensity, flat_sky(rd));
-                if (FLAT && bounce == 0u) fog = sky;
+                const float z = flat_z(rd);
+                if (FLAT && idx < 0) sky = scale(sc.minIntensity, flat_sky(z));
+                if (FLAT && bounce == 0u) fog_nan = z != z;
                 if (idx < 0) {                                           // RK:122-126
                     if (FLAT) color = divs(add(scale(sum, color), scale(affect, sky)), next);
                     else missed = true;
@@ -860,7 +883,6 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
                     const v3 dl = sub(ro, sc.lightPos);
                     const float len = length(dl);
                     sdir = divs(dl, len);                                    // RK:147: normalize(dl), its length kept for claim D
-                    distance = length_of_unit(sdir);                         // RK:148
                     decided = shadow_decided(sc.lightPos, light_l1, sdir, len, centre, hit_g.w);
                     if (!decided) {
                         shadow = true;                                       // RK:153 next
@@ -868,13 +890,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
                     }
 #ifdef RT_BVH_COUNT
                     if (RT_BVH_COUNT == 16) nrays += decided ? 1u : 0u;      // shadow rays settled without a walk (lane)
-#else
-                    if (decided) ++nrays;                                    // the shadow ray the reference casts here: counted, not walked
 #endif
                 }
             }
             if (shadow_done || decided) {
                 // a settled shadow ray has a hit that is not at the shaded point: RK:165, like "no hit"
+                const float distance = length_of_unit(sdir);                 // RK:148, taken here from the direction the path carries anyway
                 const float intensity = light_term(sc, ro, normal, sdir, distance, !decided && idx >= 0, t);
                 const v3 blended = scale(intensity, albedo);                 // RK:133-135
                 color = divs(add(scale(sum, color), scale(affect, blended)), next);   // RK:136
@@ -886,9 +907,12 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
                 if (!finished) { node = 0u; t = 9999.0f; idx = -1; }         // next reflection ray
             }
         }
+#ifndef RT_BVH_COUNT
+        nrays += (uint32_t)__popcll(__ballot(decided));                      // the shadow ray the reference casts there: counted, not walked
+#endif
         if (finished) {
             if (FLAT) {
-                reinterpret_cast<uint32_t*>(A.out)[opix] = compose_pixel_sky(fog, color, dist);   // RK:91-98
+                reinterpret_cast<uint32_t*>(A.out)[opix] = compose_pixel_sky(scale(sc.minIntensity, flat_sky(fog_nan ? __builtin_nanf("") : 0.0f)), color, dist);   // RK:91-98
             } else {
                 // dist is +0 or a hit distance > 0.001: its sign bit is free for the flag
                 A.fin[2u * opix] = make_float4(color.x, color.y, color.z, __uint_as_float(__float_as_uint(dist) | (missed ? 0x80000000u : 0u)));
@@ -904,8 +928,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 16 ? 4 : 6) void bvh_pixels(co
         const uint32_t w = (blockIdx.x * WAVES + wave) % 8192u;
         g_wave_clock[3 * w] = clk0; g_wave_clock[3 * w + 1] = clk_x ? clk_x : clk0; g_wave_clock[3 * w + 2] = wall_clock64();
     }
-#endif
     count_rays(A.rays, nrays);
+#else
+    count_rays(A.rays, lane == 0u ? nrays : 0u);
+#endif
 }
 
 // Textured sky: the second half of every pixel of bvh_pixels<..., FLAT = false>.  In the state machine the

@@ -4,17 +4,19 @@
 build and the totals go to <out>/<KEY>__counts.json, which tools/pmc_summary.py folds into profiles/traffic.json and
 bench.py prices as roofline.useful / lanes_busy.
 
-    python tools/collect_counts.py --build                      (build container: cross-compiles tools/bin/librt355_c{1,5,6,8,16,17,18}.so)
+    python tools/collect_counts.py --build                      (build container: cross-compiles tools/bin/librt355_c{1,5,6,8,16,17,18,19,20}.so)
     python tools/collect_counts.py C3 gpurun_out/r03            (GPU box: runs them, writes gpurun_out/r03/C3-fast-v0-n1__counts.json)
 
 modes: 1 trips of the walk loop x 2 (a trip is four steps of every lane of a wave), 5 literal evaluations (lane),
        6 leaf tests by a lane with a live ray, 8 inner-node tests by a lane with a live ray,
        16 shadow rays settled by the sphere they start from, without a walk (lane; rt_bvh.hip: shadow_decided),
        17 shadow walks that a suspension could end because they hold a blocker (lane; rt_bvh.hip: shadow_blocked), 18 the lane-steps
-       those walks go on for (modes 17 and 18 let them go on and count; every other build ends them)."""
+       those walks go on for (modes 17 and 18 let them go on and count; every other build ends them),
+       19 executions of the hand-out block of the outer loop (wave: idle lanes take pixels; primary_dir used to run there),
+       20 tile generations (wave: primary_dir of a whole 8x8 tile, all 64 lanes; rt_bvh.hip: tile_dir)."""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MODES = (1, 5, 6, 8, 16, 17, 18)
+MODES = (1, 5, 6, 8, 16, 17, 18, 19, 20)
 
 
 def build():
@@ -51,7 +53,7 @@ def main():
     wave_steps = 2 * c[1]
     res = {"rays": base["counter"], "kernel_id": base["kernel_id"], "node_and_leaf_tests": c[6] + c[8], "leaf_tests": c[6], "inner_node_tests": c[8],
            "literal_tests": c[5], "shadow_decided": c[16], "rays_walked": base["counter"] - c[16],
-           "shadow_walks_ended_at_a_suspension": c[17], "lane_steps_those_walks_had_left": c[18], "wave_steps": wave_steps, "lanes_busy": (c[6] + c[8]) / (64.0 * wave_steps),
+           "shadow_walks_ended_at_a_suspension": c[17], "lane_steps_those_walks_had_left": c[18], "handout_blocks": c[19], "tile_generations": c[20], "wave_steps": wave_steps, "lanes_busy": (c[6] + c[8]) / (64.0 * wave_steps),
            "note": "counting builds of rt_bvh.hip (tools/collect_counts.py), one frame of %s" % cfg}
     os.makedirs(out, exist_ok=True)
     path = os.path.join(out, "%s-fast-v0-n1__counts.json" % cfg)
