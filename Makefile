@@ -7,7 +7,7 @@ HIPFLAGS := -O3 -std=c++17 -fPIC --offload-arch=$(ARCH) -fno-fast-math -Wall -Wn
 SRCS     := $(sort $(wildcard $(CSRC)/*.hip $(CSRC)/*.h)) include/rt355.h
 # identity of the build: profiles (profiles/traffic.json) are evidence for the sources they were taken with
 BUILD_ID := $(shell cat $(SRCS) | sha256sum | cut -c1-16)
-OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o $(CSRC)/rt_query.o $(CSRC)/rt_shade.o $(CSRC)/rt_sample.o $(CSRC)/rt_gbuffer.o $(CSRC)/rt_ao.o $(CSRC)/rt_refit.o $(CSRC)/rt_build.o $(CSRC)/rt_tlas.o $(CSRC)/rt_closest.o
+OBJS     := $(CSRC)/rt_api.o $(CSRC)/rt_kernels.o $(CSRC)/rt_bvh.o $(CSRC)/rt_triangles.o $(CSRC)/rt_assemble.o $(CSRC)/rt_comm.o $(CSRC)/rt_query.o $(CSRC)/rt_shade.o $(CSRC)/rt_sample.o $(CSRC)/rt_gbuffer.o $(CSRC)/rt_ao.o $(CSRC)/rt_refit.o $(CSRC)/rt_build.o $(CSRC)/rt_tlas.o $(CSRC)/rt_closest.o $(CSRC)/rt_deform.o
 
 all: lib oracle node
 
@@ -61,6 +61,11 @@ $(CSRC)/rt_tlas.o: $(CSRC)/rt_tlas.hip $(CSRC)/rt_tlas_build.h $(CSRC)/rt_build.
 # closest-point queries: float64 leaves that must equal the host model's bit for bit; rt_query.o's flags exactly.  rt_closest.h
 # holds the arithmetic and the walk and is shared with the host model
 $(CSRC)/rt_closest.o: $(CSRC)/rt_closest.hip $(CSRC)/rt_closest.h $(CSRC)/rt_tlas_build.h $(CSRC)/rt_blas_build.h $(CSRC)/rt_query_device.h $(CSRC)/rt_query_form.h $(CSRC)/rt_tri_device.h $(CSRC)/rt_device.h $(CSRC)/rt_types.h $(CSRC)/rt_tri_types.h include/rt355.h
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
+
+# device mesh deformation: float32 flat normals that must equal the host model's bit for bit; the exact kernels' flags.
+# rt_deform.h holds the arithmetic and is shared with the host model
+$(CSRC)/rt_deform.o: $(CSRC)/rt_deform.hip $(CSRC)/rt_deform.h include/rt355.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -fno-slp-vectorize -c $< -o $@
 
 $(CSRC)/rt_assemble.o: $(CSRC)/rt_assemble.hip $(CSRC)/rt_types.h include/rt355.h

@@ -26,6 +26,7 @@ RT355_MAX_HITS = 8       # the largest k of rt_trace_rays_multi
 RT355_MAX_AO_RAYS = 64   # the largest k of rt_render_ao
 RT_SHADE_COMPOSE = 1     # flags of rt_shade_rays: r, g, b is pixelColor (RK:91-96) instead of rayColor
 RT355_MAX_SUPERSAMPLE = 4   # the largest s of rt_render_samples
+RT_DEFORM_FLAT_NORMALS = 1  # flags of rt_deform_triangles: the three corners get the unit normal of the new triangle
 
 # every symbol include/rt355.h declares (tests check the library exports each of them)
 SYMBOLS = [
@@ -52,6 +53,7 @@ SYMBOLS = [
     "rt_write_instance_masks", "rt_set_query_masks",
     "rt_build_tlas", "rt_build_tlas_device", "rt_build_tlas_host", "rt_read_blas", "rt_read_blas_lookup",
     "rt_closest_points", "rt_closest_points_host", "rt_closest_points_model",
+    "rt_deform_triangles", "rt_deform_triangles_host", "rt_deform_triangles_model", "rt_update_triangles_device", "rt_read_triangles",
 ]
 
 # rt_kernel_id (include/rt355.h): which kernel form rendered a frame
@@ -268,6 +270,11 @@ def load():
         "rt_closest_points_host": (ctypes.c_int, [vp, vp, u32, vp]),
         "rt_closest_points_model": (ctypes.c_int, [vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, vp, u32, u32, vp,
                                                    ctypes.POINTER(ctypes.c_uint64)]),
+        "rt_deform_triangles": (ctypes.c_int, [vp, u32, u32, vp, u32, vp, vp, u32, vp]),
+        "rt_deform_triangles_host": (ctypes.c_int, [vp, u32, u32, vp, u32, vp, vp, u32]),
+        "rt_deform_triangles_model": (ctypes.c_int, [vp, u32, u32, u32, vp, u32, vp, vp, u32]),
+        "rt_update_triangles_device": (ctypes.c_int, [vp, u32, u32, vp, vp]),
+        "rt_read_triangles": (ctypes.c_int, [vp, u32, u32, fp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)

@@ -23,6 +23,7 @@
 #include "rt_tlas_build.h"
 #include "rt_tlas_fit.h"
 #include "rt_closest.h"
+#include "rt_deform.h"
 
 thread_local std::string g_rt_err;
 thread_local int g_rt_kernel_id = 0;
@@ -1663,6 +1664,109 @@ int rt_read_nodes(rt_ctx* c, uint32_t first_node, uint32_t n, float* dst) {
         const uint32_t m = std::min(n, head - first_node);
         std::memcpy(dst, &c->inst.head[(size_t)first_node * 8u], (size_t)m * 32u);
     }
+    return RT_OK;
+}
+
+// ---- device mesh deformation (rt_deform.h: the arithmetic and the host model; rt_deform.hip: the kernel) -----------------------
+
+extern "C++" { RtDeformLaunch rt_deform_launch = nullptr; }        // set by rt_deform.o (rt_deform.h)
+
+int rt_deform_triangles_model(float* triangles, uint32_t n_triangles, uint32_t first, uint32_t n, const float* vertices, uint32_t V,
+                              const uint32_t* faces, const float* normals, uint32_t flags) {
+    const char* why = "";
+    const int rc = rt_df_model(triangles, n_triangles, first, n, vertices, V, faces, normals, flags, &why);
+    if (rc != RT_OK) { char msg[200]; std::snprintf(msg, sizeof msg, "rt_deform_triangles_model: %s", why); return fail(rc, msg); }
+    return RT_OK;
+}
+
+// A triangle write from device memory produced on `hip_stream`: rt_update_triangles' contract.  Drains, orders the context's
+// stream behind the scene-update event and waits (the host does) for the caller's stream.
+static int device_source_begin(rt_ctx* c, void* hip_stream) {
+    RT_HIP(hipSetDevice(c->device));
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    if (c->scene_stream && c->scene_stream != c->stream) RT_HIP(hipStreamWaitEvent(c->stream, c->ev_scene, 0));
+    if (hip_stream) RT_HIP(hipStreamSynchronize(static_cast<hipStream_t>(hip_stream)));
+    return RT_OK;
+}
+// ... and its end: the scene-update event behind the work, and the work complete, so that the caller's arrays are free
+static int device_source_end(rt_ctx* c) {
+    RT_HIP(hipEventRecord(c->ev_scene, c->stream));     // frames and queries on other streams wait for it (the scene-update event)
+    c->scene_stream = c->stream;
+    RT_HIP(hipStreamSynchronize(c->stream));
+    return RT_OK;
+}
+
+// vertices / faces / normals: device memory the caller's stream `hip_stream` produced (device == true), or host memory
+static int deform_triangles(rt_ctx* c, const char* who, uint32_t first, uint32_t n, const float* vertices, uint32_t V,
+                            const uint32_t* faces, const float* normals, uint32_t flags, bool device, void* hip_stream) {
+    char msg[200];
+    if (!c) { std::snprintf(msg, sizeof msg, "%s: ctx is NULL", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (const char* bad = rt_df_check_flags(normals, flags)) { std::snprintf(msg, sizeof msg, "%s: %s", who, bad); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (c->scene_kind != 1 || !c->d_tri.used) { std::snprintf(msg, sizeof msg, "%s: no triangle scene (rt_write_triangles first)", who); return fail(RT_ERR_STATE, msg); }
+    const uint32_t n_tri = (uint32_t)std::min(c->d_tri.used / 160u, c->d_tri.cap / 160u);
+    if (!rt_df_in_range(first, n, n_tri)) { std::snprintf(msg, sizeof msg, "%s: first + n is beyond the triangles written", who); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (n == 0u) return RT_OK;
+    if (const char* bad = rt_df_check_arrays(n, vertices, V, faces)) { std::snprintf(msg, sizeof msg, "%s: %s", who, bad); return fail(RT_ERR_INVALID_ARG, msg); }
+    if (device && ((reinterpret_cast<uintptr_t>(vertices) | reinterpret_cast<uintptr_t>(faces) | reinterpret_cast<uintptr_t>(normals)) & 3u)) {
+        std::snprintf(msg, sizeof msg, "%s: device pointers must be 4-byte aligned", who);
+        return fail(RT_ERR_INVALID_ARG, msg);
+    }
+    { int rc = device_source_begin(c, device ? hip_stream : nullptr); if (rc != RT_OK) return rc; }
+    RtDeformArgs a;
+    a.tri = static_cast<float*>(c->d_tri.p); a.n_tri = n_tri; a.first = first; a.n = n;
+    a.vertices = vertices; a.V = V; a.faces = faces; a.normals = normals; a.flags = flags;
+    if (!device) {
+        // staged: without faces only the first 3 n vertices (and normals) are read
+        const size_t v_bytes = (size_t)(faces ? V : 3u * n) * 12u, f_bytes = faces ? (size_t)n * 12u : 0u, n_bytes = normals ? v_bytes : 0u;
+        { int rc = grow_buf(c, c->d_deform, v_bytes + f_bytes + n_bytes); if (rc != RT_OK) return rc; }
+        char* base = static_cast<char*>(c->d_deform.p);
+        RT_HIP(hipMemcpyAsync(base, vertices, v_bytes, hipMemcpyHostToDevice, c->stream));
+        if (faces) RT_HIP(hipMemcpyAsync(base + v_bytes, faces, f_bytes, hipMemcpyHostToDevice, c->stream));
+        if (normals) RT_HIP(hipMemcpyAsync(base + v_bytes + f_bytes, normals, n_bytes, hipMemcpyHostToDevice, c->stream));
+        RT_HIP(hipStreamSynchronize(c->stream));        // pageable sources
+        a.vertices = reinterpret_cast<const float*>(base);
+        a.faces = faces ? reinterpret_cast<const uint32_t*>(base + v_bytes) : nullptr;
+        a.normals = normals ? reinterpret_cast<const float*>(base + v_bytes + f_bytes) : nullptr;
+    }
+    // the corner array follows: rebuilt whole by the next refit, frame or query (ensure_corners), as after rt_update_triangles
+    c->corners_valid = false;
+    if (!rt_deform_launch) return fail(RT_ERR_UNSUPPORTED, "rt_deform_triangles: this build holds no deformation kernel (rt_deform.o is not linked)");
+    RT_HIP(rt_deform_launch(a, c->stream));
+    return device_source_end(c);
+}
+
+int rt_deform_triangles(rt_ctx* c, uint32_t first, uint32_t n, const float* vertices, uint32_t V, const uint32_t* faces,
+                        const float* normals, uint32_t flags, void* hip_stream) {
+    return deform_triangles(c, "rt_deform_triangles", first, n, vertices, V, faces, normals, flags, true, hip_stream);
+}
+int rt_deform_triangles_host(rt_ctx* c, uint32_t first, uint32_t n, const float* vertices, uint32_t V, const uint32_t* faces,
+                             const float* normals, uint32_t flags) {
+    return deform_triangles(c, "rt_deform_triangles_host", first, n, vertices, V, faces, normals, flags, false, nullptr);
+}
+
+int rt_update_triangles_device(rt_ctx* c, uint32_t first, uint32_t n, const float* records_dev, void* hip_stream) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_update_triangles_device: ctx is NULL");
+    if (c->scene_kind != 1 || !c->d_tri.used) return fail(RT_ERR_STATE, "rt_update_triangles_device: no triangle scene (rt_write_triangles first)");
+    if ((uint64_t)first + n > std::min(c->d_tri.used, c->d_tri.cap) / 160u) return fail(RT_ERR_INVALID_ARG, "rt_update_triangles_device: first + n is beyond the triangles written");
+    if (n == 0u) return RT_OK;
+    if (!records_dev) return fail(RT_ERR_INVALID_ARG, "rt_update_triangles_device: records_dev is NULL");
+    if (reinterpret_cast<uintptr_t>(records_dev) & 3u) return fail(RT_ERR_INVALID_ARG, "rt_update_triangles_device: records_dev must be 4-byte aligned");
+    { int rc = device_source_begin(c, hip_stream); if (rc != RT_OK) return rc; }
+    c->corners_valid = false;                           // as rt_update_triangles
+    RT_HIP(hipMemcpyAsync(static_cast<char*>(c->d_tri.p) + (size_t)first * 160u, records_dev, (size_t)n * 160u, hipMemcpyDeviceToDevice, c->stream));
+    return device_source_end(c);
+}
+
+int rt_read_triangles(rt_ctx* c, uint32_t first, uint32_t n, float* dst) {
+    if (!c) return fail(RT_ERR_INVALID_ARG, "rt_read_triangles: ctx is NULL");
+    if ((uint64_t)first + n > c->d_tri.used / 160u) return fail(RT_ERR_INVALID_ARG, "rt_read_triangles: first + n is beyond the triangles written");
+    if (n == 0u) return RT_OK;
+    if (!dst) return fail(RT_ERR_INVALID_ARG, "rt_read_triangles: dst is NULL");
+    RT_HIP(hipSetDevice(c->device));
+    { int rc = drain(c); if (rc != RT_OK) return rc; }
+    if (c->scene_stream && c->scene_stream != c->stream) RT_HIP(hipStreamWaitEvent(c->stream, c->ev_scene, 0));
+    RT_HIP(hipMemcpyAsync(dst, static_cast<const char*>(c->d_tri.p) + (size_t)first * 160u, (size_t)n * 160u, hipMemcpyDeviceToHost, c->stream));
+    RT_HIP(hipStreamSynchronize(c->stream));
     return RT_OK;
 }
 

@@ -161,6 +161,7 @@ struct rt_ctx {
     } refit;
     DevBuf d_refit_plan;
     DevBuf d_build;                              // scratch of rt_build_blas (rt_build.h: RtBuildArgs), kept between calls
+    DevBuf d_deform;                             // staging of rt_deform_triangles_host: vertices, faces, normals; kept between calls
     DevBuf d_tri_dbg;                            // development builds: the triangle kernel's per-workgroup timeline
     // Ray queries (rt_trace_rays_host / rt_pick): query_stream, staging buffers that grow as needed, and ev_query behind the
     // latest query on any stream -- scene writes wait for it as they wait for the frames in flight (rt_drain)

@@ -122,15 +122,112 @@ class RendererRaytracing:
     # ---- deforming meshes: partial triangle writes and the device refit (rt_update_triangles / rt_refit_blas / rt_read_nodes) ----
     def update_triangles(self, first, records):
         """Replaces triangle records [first, first + n) -- (n, 40) float32 in pack_triangles' layout -- on the device and in the
-        scene's packed `triangles` (the scene is uploaded first if it has not been: recalculateScene()).  No node changes: follow
-        it with refit().  Drains the frames in flight."""
-        rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 40)
+        scene's packed `triangles` (the scene is uploaded first if it has not been: recalculateScene()).  A contiguous float32
+        (n, 40) torch tensor on this renderer's device is copied there, on torch's current stream (rt_update_triangles_device).  No
+        node changes: follow it with refit().  Drains the frames in flight."""
         first = int(first)
+        if self._is_tensor(records):                                               # (n, 40) on this renderer's device: read there
+            self._check_deform_tensor("update_triangles", "records", records, ((None, 40),))
+            self.recalculateScene()
+            with self._current_stream(records.device) as stream:
+                abi.check(self._lib.rt_update_triangles_device(self._ctx, first, records.shape[0], ctypes.c_void_p(records.data_ptr()), stream), self._ctx)
+            self._mirror_triangles(first, self.read_triangles(first, records.shape[0]))
+            return
+        rec = np.ascontiguousarray(records, dtype=np.float32).reshape(-1, 40)
         self.recalculateScene()
         abi.check(self._lib.rt_update_triangles(self._ctx, first, rec.shape[0], rec.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._ctx)
+        self._mirror_triangles(first, rec)
+
+    def _mirror_triangles(self, first, rec):
         tris = np.array(self.scene.static["triangles"], dtype=np.float32)          # a copy: packed arrays may be shared between scenes
         tris[first:first + rec.shape[0]] = rec
         self.scene.static["triangles"] = tris
+
+    @staticmethod
+    def _is_tensor(x):
+        return x is not None and type(x).__module__.split(".")[0] == "torch"
+
+    def _check_deform_tensor(self, who, name, t, shapes, dtype="float32"):
+        """A contiguous tensor of `dtype` on this renderer's device with one of `shapes` (None: any extent), as build_top_level
+        asks of its matrices."""
+        import torch
+        fits = any(len(s) == t.dim() and all(w is None or w == g for w, g in zip(s, t.shape)) for s in shapes)
+        if t.dtype != getattr(torch, dtype) or not fits or not t.is_contiguous():
+            want = " or ".join("(%s)" % ", ".join("n" if w is None else str(w) for w in s) for s in shapes)
+            raise ValueError("%s: %s must be a contiguous %s %s tensor" % (who, name, dtype, want))
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError("%s: %s must live on cuda:%d, this renderer's device" % (who, name, self.device))
+
+    def deform(self, first, vertices, faces=None, normals=None, flat_normals=False, refit=True):
+        """New corner positions for triangles [first, first + T) from vertex arrays, with no 40-float records on the caller's
+        side.  vertices: float32 (V, 3), or (T, 3, 3) -- three corners per triangle; faces: int32 (T, 3) indices into
+        `vertices` (an index at or beyond V reads vertex V - 1; negative ones too), None: triangle i takes vertices 3 i .. 3 i + 2;
+        normals: float32, per vertex like `vertices`, written to the corners' normals; flat_normals: the three corners get the
+        unit normal of the new triangle instead (not together with normals); with neither the normals stay.  uv, colour and
+        every other triangle keep their bytes.  torch tensors on this renderer's device are read there, on torch's current
+        stream (rt_deform_triangles), and nothing crosses to the host but the read-back below; numpy arrays are staged
+        (rt_deform_triangles_host).  All arrays of one call are of one kind.  Afterwards the scene's packed `triangles` are
+        the device's bytes for the range, so scene.to_packed() describes exactly what frames read.  refit: refit() follows --
+        new boxes for every bottom-level tree.  The top-level tree made by scene.update(dt) has placeholder boxes and needs
+        nothing; a tight one (build_top_level()) must be built again after a deformation that grows a root box: call
+        build_top_level() afterwards.  Drains the frames in flight."""
+        who = "deform"
+        first = int(first)
+        if flat_normals and normals is not None:
+            raise ValueError("deform: flat_normals and normals exclude each other")
+        flags = abi.RT_DEFORM_FLAT_NORMALS if flat_normals else 0
+        arrays = [a for a in (vertices, faces, normals) if a is not None]
+        on_device = self._is_tensor(vertices)
+        if any(self._is_tensor(a) != on_device for a in arrays):
+            raise ValueError("deform: vertices, faces and normals must be all torch tensors or all numpy arrays")
+        if on_device:
+            per_vertex = ((None, 3), (None, 3, 3))
+            self._check_deform_tensor(who, "vertices", vertices, per_vertex)
+            if faces is not None:
+                self._check_deform_tensor(who, "faces", faces, ((None, 3),), "int32")
+            if normals is not None:
+                self._check_deform_tensor(who, "normals", normals, per_vertex)
+                if normals.numel() != vertices.numel():
+                    raise ValueError("deform: normals must have one row per vertex")
+            V = vertices.numel() // 3
+            n = faces.shape[0] if faces is not None else V // 3
+            ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
+        else:
+            vertices = np.ascontiguousarray(vertices, dtype=np.float32)
+            if vertices.ndim not in (2, 3) or vertices.shape[1:] not in ((3,), (3, 3)):
+                raise ValueError("deform: vertices must be (V, 3) or (T, 3, 3)")
+            V = vertices.size // 3
+            if faces is not None:
+                faces = np.ascontiguousarray(np.asarray(faces).astype(np.int64).astype(np.uint32))
+                if faces.ndim != 2 or faces.shape[1] != 3:
+                    raise ValueError("deform: faces must be (T, 3)")
+            if normals is not None:
+                normals = np.ascontiguousarray(normals, dtype=np.float32)
+                if normals.size != vertices.size:
+                    raise ValueError("deform: normals must have one row per vertex")
+            n = faces.shape[0] if faces is not None else V // 3
+            ptr = lambda a: None if a is None else ctypes.c_void_p(a.ctypes.data)
+        if faces is None and V != 3 * n:
+            raise ValueError("deform: without faces the vertex count must be a multiple of 3")
+        self.recalculateScene()
+        head = (self._ctx, first, n, ptr(vertices), V, ptr(faces), ptr(normals), flags)
+        if on_device:
+            with self._current_stream(vertices.device) as stream:
+                abi.check(self._lib.rt_deform_triangles(*head, stream), self._ctx)
+        else:
+            abi.check(self._lib.rt_deform_triangles_host(*head), self._ctx)
+        self._mirror_triangles(first, self.read_triangles(first, n))
+        if refit:
+            self.refit()
+
+    def read_triangles(self, first=0, n=None):
+        """(n, 40) float32: triangle records [first, first + n) on the device, as the next frame would read them (n None: up to the
+        scene's last triangle).  A diagnostic: it waits for the frames in flight."""
+        first = int(first)
+        n = self.scene.triangleCount - first if n is None else int(n)
+        out = np.zeros((max(n, 0), 40), dtype=np.float32)
+        abi.check(self._lib.rt_read_triangles(self._ctx, first, n, out.ctypes.data_as(ctypes.POINTER(ctypes.c_float))), self._ctx)
+        return out
 
     def refit(self, roots=None):
         """New boxes for the bottom-level trees under `roots` (node indices: a mesh's root_node; None: every root the instances

@@ -759,6 +759,48 @@ int rt_read_nodes(rt_ctx* ctx, uint32_t first_node, uint32_t n, float* dst);
 int rt_refit_plan(const float* nodes, uint32_t n_nodes, uint32_t n_tri_lookup, const uint32_t* roots, uint32_t n_roots,
                   uint32_t* plan, uint32_t cap_nodes, uint32_t* n_plan);
 
+/* ---- device mesh deformation: the vertices of a deforming mesh from device memory into the triangle records ---------------------- */
+
+#define RT_DEFORM_FLAT_NORMALS 1u   /* flags of rt_deform_triangles: the three corners get the unit normal of the new triangle */
+
+/* rt_deform_triangles: rewrites the positions (and optionally the normals) of triangle records [first, first + n) from vertex arrays
+ * in DEVICE memory, produced on `hip_stream` (NULL: none to wait for) -- rt_update_triangles for callers whose vertices live on the
+ * device and who do not keep 160-byte records.  For triangle i of the call and corner c: the vertex index is
+ * k = faces ? min(faces[3 i + c], V - 1) : 3 i + c; words 12 c + 0..2 of record first + i become vertices[3 k + 0..2] and, when
+ * `normals` is given, words 12 c + 4..6 become normals[3 k + 0..2], all copied bit for bit (NaN and inf as they are).  With
+ * RT_DEFORM_FLAT_NORMALS the three corners get n / len instead, computed from the new corners A, B, C in float32 with one rounding
+ * per operation: e1 = B - A, e2 = C - A, n = (e1.y e2.z - e1.z e2.y, e1.z e2.x - e1.x e2.z, e1.x e2.y - e1.y e2.x),
+ * len = sqrtf((n.x n.x + n.y n.y) + n.z n.z), IEEE division; no guards (a zero-area triangle stores what 0 / 0 gives; no ray
+ * test hits it).  No other word of a record (3, 7, 8..11 of each corner, 36..39) and no other record is written
+ * (csrc/rt_deform.h is the definition; csrc/rt_deform.hip stores only the words named).
+ * The contract is rt_update_triangles': a scene-setup call, synchronous; it waits for the frames in flight, synchronises
+ * hip_stream before it reads the caller's arrays, runs on the context's stream behind the scene-update event and records that
+ * event, so frames and queries on any stream see the new records; on return the caller's arrays are free.  It changes no node and
+ * no lookup slot -- follow it with rt_refit_blas (a cached refit plan stays valid, the pair records are not marked stale) and,
+ * for a tight top level, rt_build_tlas.  The library's corner array follows by itself.
+ * Checks, in this order: a NULL context, unknown flag bits, or RT_DEFORM_FLAT_NORMALS together with normals: RT_ERR_INVALID_ARG;
+ * no triangle scene (a sphere scene too): RT_ERR_STATE; first + n (taken in 64 bits) beyond the triangles written:
+ * RT_ERR_INVALID_ARG, nothing changed; n == 0: RT_OK; NULL vertices, V == 0, no faces and V < 3 n (in 64 bits), or -- the
+ * device form -- a pointer that is not 4-byte aligned: RT_ERR_INVALID_ARG.
+ *
+ * rt_deform_triangles_host: the same with the arrays in HOST memory, staged through a buffer the context owns.
+ * rt_deform_triangles_model: the same arithmetic, serially, on caller arrays (triangles: n_triangles records of 40 floats, changed
+ * in place), with no device and no context; the same checks, RT_ERR_STATE when `triangles` is NULL or empty.
+ * rt_update_triangles_device: rt_update_triangles with the records in DEVICE memory (4-byte aligned), produced on hip_stream. */
+int rt_deform_triangles(rt_ctx* ctx, uint32_t first, uint32_t n, const float* vertices /* dev [V][3] */, uint32_t V,
+                        const uint32_t* faces /* dev [n][3] or NULL */, const float* normals /* dev [V][3] or NULL */,
+                        uint32_t flags, void* hip_stream);
+int rt_deform_triangles_host(rt_ctx* ctx, uint32_t first, uint32_t n, const float* vertices /* host [V][3] */, uint32_t V,
+                             const uint32_t* faces /* host [n][3] or NULL */, const float* normals /* host [V][3] or NULL */,
+                             uint32_t flags);
+int rt_deform_triangles_model(float* triangles, uint32_t n_triangles, uint32_t first, uint32_t n, const float* vertices, uint32_t V,
+                              const uint32_t* faces, const float* normals, uint32_t flags);
+int rt_update_triangles_device(rt_ctx* ctx, uint32_t first, uint32_t n, const float* records_dev, void* hip_stream);
+
+/* Diagnostic: rt_read_nodes for the triangle records -- `n` records (40 f32 each) starting at record `first`, as the next frame
+ * would read them.  Waits for the frames in flight.  first + n beyond the triangles written: RT_ERR_INVALID_ARG. */
+int rt_read_triangles(rt_ctx* ctx, uint32_t first, uint32_t n, float* dst);
+
 /* ---- device BLAS builds: the builder's SAH tree of a mesh, made on the device ------------------------------------------------------ */
 
 typedef struct rt_blas_range {
